@@ -15,8 +15,13 @@ each rank trains on ``--batch-size`` sequences of ``--seq-len`` steps.
     python bench.py --gpus 8                          # 8 rank processes started by bench.py itself
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8
 
-Rank 0 prints ONE JSON line. The actor and end-to-end numbers are measured *outside* the timed learner region, on
-EVERY rank (one actor runtime per GPU), and reported as node aggregates (sums over ranks) with per-rank lists:
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times ``--steps`` steps (``ms_per_step`` is the time of one)
+and prints; ``--dump-outputs DIR`` also writes what the last timed step returned and updated (``dump_outputs``: the
+metrics, the flat parameters and gradient) as ``DIR/<name>.npy`` — the seeds are fixed, so two builds run with the same
+arguments are comparable output for output. Everything below is measured only with ``--full`` (null otherwise), as is
+the cross-rank weight hash (``dp_replicas_identical``). The actor and end-to-end numbers are measured *outside* the
+timed learner region, on EVERY rank (one actor runtime per GPU), and reported as node aggregates (sums over ranks)
+with per-rank lists:
 
 * ``actor.steps_per_s`` — player-steps/s of the whole self-play runtime (actor/vec.py), ``actor.policy_step_per_s``
   the batched GPU policy step alone (raw unit records staged and featurized on the GPU, the runtime's path;
@@ -67,6 +72,13 @@ def parse():
     ap.add_argument('--gpus', type=int, default=int(os.environ.get('WORLD_SIZE', 1)))
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run every other measurement and check (the *-extra learner '
+                         'variants, the actor runtime, the node loops, the DP replica hash); a plain run times the '
+                         'headline steps only and reports those fields as null')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps write what the last timed step returned and left behind (its metrics, '
+                         'the updated flat parameters, the reduced flat gradient) as DIR/<name>.npy (float32)')
     ap.add_argument('--batch-size', type=int, default=8, help='sequences per GPU per step (reference deploy: 8)')
     ap.add_argument('--seq-len', type=int, default=1400, help='steps per sequence (reference deploy: 1400)')
     ap.add_argument('--model', default='lstm512')
@@ -152,6 +164,26 @@ def parse():
 def progress(msg: str):
     """Phase markers on stderr (one line each, flushed) so a long multi-rank run shows where it is."""
     print(f'[bench r{os.environ.get("RANK", "0")} {time.strftime("%H:%M:%S")}] {msg}', file=sys.stderr, flush=True)
+
+
+DUMP_MAX_ELEMS = 6 << 20    # per array (24 MB of float32): the two flat buffers and the metrics stay under 64 MB
+
+
+def dump_outputs(out_dir: str, metrics, learner) -> None:
+    """``--dump-outputs``: what a caller of the timed step holds after the last timed step — the step's metric
+    tensors (``<metric>.npy``, '/' written as '_') and the learner's state the step wrote: the updated flat parameter
+    buffer (``params.npy``) and the flat gradient it was updated with (``grad.npy``) — as float32 ``.npy`` files. An
+    array of more than ``DUMP_MAX_ELEMS`` elements is written as a fixed seeded sample of that many (sorted indices)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k.replace('/', '_'): v for k, v in metrics.items()}
+    arrays['params'] = learner.flat.flat
+    arrays['grad'] = learner.flat.grad
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _free_port() -> int:
@@ -246,6 +278,8 @@ def main():
 
     cfg = get_config(args.model)
     trace = os.environ.get('DCA_BENCH_TRACE') == '1'
+    full = args.full
+    last_out = {}       # what the last step of the latest run() returned (for --dump-outputs)
 
     def run(precision, cfg=cfg, B=None, S=None, backend=None, steps=None, warmup=None, vtrace=False):
         """Build a learner of this precision and time ``args.steps`` DP PPO steps (``B`` sequences of ``S`` steps,
@@ -307,6 +341,7 @@ def main():
             elapsed = float(t.item())
         loss_last = float(m['loss'])
         learner.check_error()       # a persistent-kernel timeout would invalidate the measurement
+        last_out['metrics'] = m
         return elapsed, loss_first, loss_last, learner, policy
 
     progress(f'learner {args.precision}: world {world}, device {device}')
@@ -321,13 +356,16 @@ def main():
         comm['rank'] = rank
     step_mode = {'hipgraph': learner.graph is not None, 'dp_split_overlap': bool(getattr(learner, '_split', False)),
                  'dist_backend': dist.get_backend() if world > 1 else None}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out['metrics'], learner)
     # DP replicas must hold bit-identical weights after the timed steps (checked across ranks below)
-    weights_sha = hashlib.sha256(learner.flat.flat.detach().cpu().numpy().tobytes()).hexdigest()[:16]
+    weights_sha = (hashlib.sha256(learner.flat.flat.detach().cpu().numpy().tobytes()).hexdigest()[:16]
+                   if full else None)
     samples = args.batch_size * args.seq_len * world * args.steps
     value = samples / elapsed
     ms_per_step = elapsed / args.steps * 1e3
     vtr = None
-    if args.vtrace_extra and args.algo == 'ppo' and use_cuda:
+    if full and args.vtrace_extra and args.algo == 'ppo' and use_cuda:
         # the same step with the in-step V-trace (the node loop's default advantages: every minibatch's advantages and
         # value targets recomputed from the step's own values / log-probs against the behaviour log-prob)
         learner = None
@@ -339,7 +377,7 @@ def main():
         except Exception as e:
             vtr = {'error': repr(e)}
     bf16x3 = None
-    if args.bf16x3_extra and args.precision == 'fp32-exact' and use_cuda:
+    if full and args.bf16x3_extra and args.precision == 'fp32-exact' and use_cuda:
         learner = None
         try:
             e3, l30, l31, _, _ = run('fp32')
@@ -351,7 +389,7 @@ def main():
             bf16x3 = {'error': repr(e)}
 
     model_5v5 = None
-    if args.model_5v5_extra and use_cuda and not cfg.entity_attention:
+    if full and args.model_5v5_extra and use_cuda and not cfg.entity_attention:
         # BASELINE config 4: the 5v5 policy (64 unit slots, pre-LN entity self-attention) through the same fused
         # learner step, same B, S, precision and DP layout
         learner = None
@@ -366,7 +404,7 @@ def main():
             model_5v5 = {'error': repr(e)}
 
     model_5v5_exact = None
-    if args.model_5v5_exact_extra and use_cuda and not cfg.entity_attention:
+    if full and args.model_5v5_exact_extra and use_cuda and not cfg.entity_attention:
         # the 5v5 policy at the reference's precision on the fused kernels: the IEEE-fp32 twins of the attention block
         # (ops/csrc/attn_block.hip EX), the exact encoder / recurrence / heads kernels, exact split-K ∂W GEMMs
         learner = None
@@ -380,7 +418,7 @@ def main():
             model_5v5_exact = {'error': repr(e)}
 
     bptt = None
-    if (args.bptt350_extra and use_cuda and cfg.rnn == 'lstm' and not cfg.entity_attention
+    if (full and args.bptt350_extra and use_cuda and cfg.rnn == 'lstm' and not cfg.entity_attention
             and args.seq_len % 350 == 0 and args.seq_len > 350):
         # truncated BPTT (SURVEY §5 long-context row): every seq_len-step sequence trained as seq_len/350
         # independent 350-step chains that start from the (h, c) the actor stored every 350 steps (replay h0 / c0),
@@ -397,7 +435,7 @@ def main():
             bptt = {'error': repr(e)}
 
     big = {}
-    if args.big_batch_extra and use_cuda and cfg.rnn == 'lstm' and not cfg.entity_attention:
+    if full and args.big_batch_extra and use_cuda and cfg.rnn == 'lstm' and not cfg.entity_attention:
         # the same learner at 16 / 32 sequences per GPU (2 / 4 rows per XCD chain of the exact recurrence): the
         # recurrence is latency-bound, so samples per step grow faster than its time
         learner = None
@@ -420,7 +458,7 @@ def main():
         return out
 
     actor = None
-    if args.actor and use_cuda:
+    if full and args.actor and use_cuda:
         # one actor runtime per GPU, all ranks at once (node aggregate = sum): actor.steps_per_s is the whole
         # self-play runtime (actor/vec.py: native engine + featurize + reward + trajectory/rollout encoding on host
         # threads, one hipGraph policy step for every player) in player-steps/s; actor.policy_step_per_s is the
@@ -506,7 +544,7 @@ def main():
         actor['ranks'] = world
 
     e2e = None
-    if args.e2e > 0 and use_cuda and (args.e2e_mode == 'process' or world == 1):
+    if full and args.e2e > 0 and use_cuda and (args.e2e_mode == 'process' or world == 1):
         # the reference's own metric ('steps per s' incl. the wait for experience, optimizer.py:485-486) from the
         # real node loop: actor process per GPU → ONE node queue → WORLD_SIZE DotaOptimizer ranks (deploy shape
         # 8×1400, 16 seq/iteration, DDP) → rank 0 publishes the model → actors
@@ -531,7 +569,7 @@ def main():
             e2e = {'error': f'failed on rank(s) {[i for i, x in enumerate(errs) if x]}'}
 
     e2e_bf16 = None
-    if (args.e2e > 0 and args.e2e_extra > 0 and use_cuda and args.e2e_mode == 'process'
+    if (full and args.e2e > 0 and args.e2e_extra > 0 and use_cuda and args.e2e_mode == 'process'
             and args.e2e_actor_precision != 'bf16'):
         # the same node loop with the bf16 actor policy step (extra; the credited e2e runs the reference precision)
         try:
@@ -550,7 +588,7 @@ def main():
             e2e_bf16 = {'error': f'failed on rank(s) {[i for i, x in enumerate(errs) if x]}'}
 
     league_replay = None
-    if args.league_replay_extra > 0 and use_cuda and args.e2e_mode == 'process' and cfg.rnn == 'lstm':
+    if full and args.league_replay_extra > 0 and use_cuda and args.e2e_mode == 'process' and cfg.rnn == 'lstm':
         # BASELINE config 5 (presets.py league-replay): the same node loop with a PFSP league of past versions
         # (80 % of games on the latest weights), the fp8 actor policy step (actor/batched.py Fp8ActorPolicy) and an
         # on-HBM replay of --league-replay-gb GB per learner (learner/replay.py) that every minibatch is sampled from
@@ -573,7 +611,7 @@ def main():
     e2e_5v5 = None
     if args.e2e_5v5_extra < 0:
         args.e2e_5v5_extra = 15.0 if world == 1 else 0.0
-    if args.e2e_5v5_extra > 0 and use_cuda and args.e2e_mode == 'process' and args.model != '5v5':
+    if full and args.e2e_5v5_extra > 0 and use_cuda and args.e2e_mode == 'process' and args.model != '5v5':
         # BASELINE config 4 end to end: the same node loop on the 5v5 model (entity attention, the learner at the
         # headline precision), 5v5 self-play games on the VecActor (e2e_games / 5 games, 10 player slots each)
         try:
@@ -591,7 +629,7 @@ def main():
         if any(errs) and 'error' not in e2e_5v5:
             e2e_5v5 = {'error': f'failed on rank(s) {[i for i, x in enumerate(errs) if x]}'}
 
-    shas = gather(weights_sha)
+    shas = gather(weights_sha) if full else None
     hosts = gather(host)
     comms = gather(comm)
     if rank == 0:
@@ -602,6 +640,7 @@ def main():
             'n_gpus': world,
             'steps': args.steps,
             'warmup': args.warmup,
+            'full': full,
             'ms_per_step': ms_per_step,
             'higher_is_better': True,
             'scaling': 'weak',
@@ -634,7 +673,7 @@ def main():
             'learner_vtrace': vtr,
             'learner_b16': big.get('learner_b16'),
             'learner_b32': big.get('learner_b32'),
-            'dp_replicas_identical': len(set(shas)) == 1,
+            'dp_replicas_identical': len(set(shas)) == 1 if full else None,
             'dp_comm': ({'dist_backend': step_mode['dist_backend'], 'per_rank': comms,
                          'allreduce_ms_max': max((c or {}).get('allreduce_ms', 0.0) for c in comms),
                          'exposed_ms_max': max((c or {}).get('exposed_ms', 0.0) for c in comms)}

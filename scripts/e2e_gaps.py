@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""GPU occupancy of the node loop from a rocprofv3 ``--kernel-trace`` of ``bench.py --e2e`` (learner + actor process on
-one GPU): per process the kernel count, summed kernel time and busy time (union of its kernels' intervals), the
+"""GPU occupancy of the node loop from a rocprofv3 ``--kernel-trace`` of ``bench.py --full --e2e`` (learner + actor
+process on one GPU): per process the kernel count, summed kernel time and busy time (union of its kernels' intervals), the
 device's busy union, and the learner's idle gaps (no learner kernel running) by size — with how much of each gap the
 actor's kernels filled. ``python scripts/e2e_gaps.py <trace dir> [--window-s S]`` (the last S seconds, default 6).
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What runs beside the learner's persistent recurrence in the node loop: from a rocprofv3 ``--kernel-trace`` (csv) of
-``bench.py --e2e``, the per-call durations of ``lstm_team_fwd`` / ``lstm_team_bwd`` (median, mean) and, by kernel name
+``bench.py --full --e2e``, the per-call durations of ``lstm_team_fwd`` / ``lstm_team_bwd`` (median, mean) and, by kernel name
 and process, how much of the recurrence's time other kernels overlapped it. ``python scripts/e2e_overlap.py <trace dir>
 [--window-s S]``."""
 import csv

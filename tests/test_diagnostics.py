@@ -13,14 +13,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_gil_probe_sees_a_gil_holder():
-    import numpy as np
     from dotaclient_amd.utils.gilprobe import GilProbe
     p = GilProbe(slow_ms=2.0)
 
     def hog():
-        a = np.random.default_rng(0).random(4_000_000)
         for _ in range(3):
-            np.sort(a, kind='stable')        # holds the GIL for tens of ms per call
+            # one C call that keeps the GIL for tens of ms (numpy's sort of a float array releases it: on an idle
+            # machine the probe then never wakes late)
+            sum(range(5_000_000))
     th = threading.Thread(target=hog, name='hog')
     th.start()
     th.join()

@@ -1,6 +1,5 @@
 """Reference policy (compat) parity, action helpers, and the dense losses vs the reference's masked_select formula
 (optimizer.py:602-672)."""
-import importlib.util
 import os
 
 import numpy as np
@@ -12,16 +11,14 @@ from dotaclient_amd.learner.synthetic import make_batch
 from dotaclient_amd.models.policy import Policy, batched_action_masks, get_config, masked_log_softmax
 from dotaclient_amd.constants import LAYOUT_1V1
 
-REF = '/root/reference/policy.py'
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'compat_policy_reference.npz')
 
 
-def _ref_policy_module():
-    if not os.path.exists(REF):
-        pytest.skip('reference checkout not mounted')
-    spec = importlib.util.spec_from_file_location('ref_policy', REF)
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+def _golden_weights(shapes, seed=1234):
+    """The weights the recorded reference run used: per tensor (sorted by name) uniform in ±1/sqrt(fan-in) from one
+    seeded CPU generator — regenerated here instead of stored (the file holds names, shapes, inputs and outputs)."""
+    g = torch.Generator().manual_seed(seed)
+    return {k: (torch.rand(*shapes[k], generator=g) * 2 - 1) / float(shapes[k][-1]) ** 0.5 for k in sorted(shapes)}
 
 
 def _inputs(B=2, S=3, seed=0):
@@ -35,21 +32,30 @@ def _inputs(B=2, S=3, seed=0):
 
 
 def test_compat_policy_matches_reference_exactly():
-    ref = _ref_policy_module()
-    r = ref.Policy()
+    """The compat policy against a recorded run of the reference policy (tests/golden/compat_policy_reference.npz:
+    its state_dict names and shapes, the inputs of ``_inputs()``, its logits, value and masked softmax at the weights
+    of ``_golden_weights``). Same names and shapes, and the same outputs: bit for bit where the recording machine's
+    fp32 GEMM kernels are this machine's too; across CPUs torch may sum a dot product (≤ 896 terms here) in another
+    order, a few fp32 ulps (6e-8 relative each) of the result — hence rtol 1e-5 / atol 1e-6, no more."""
+    gold = np.load(GOLDEN)
+    shapes = {k[len('shape/'):]: tuple(int(n) for n in gold[k]) for k in gold.files if k.startswith('shape/')}
     m = Policy('compat')
-    assert sorted(r.state_dict()) == sorted(m.state_dict())
-    m.load_state_dict(r.state_dict(), strict=True)
+    assert sorted(shapes) == sorted(m.state_dict())
+    assert all(tuple(v.shape) == shapes[k] for k, v in m.state_dict().items())
+    m.load_state_dict(_golden_weights(shapes), strict=True)
     inp = _inputs()
-    a, va, _ = r(**inp, hidden=None)
-    b, vb, _ = m(**inp, hidden=None)
+    for k, v in inp.items():
+        torch.testing.assert_close(v, torch.from_numpy(gold['in/' + k]), rtol=0, atol=0)
+    a = {k[len('out/'):]: torch.from_numpy(gold[k]) for k in gold.files if k.startswith('out/')}
+    with torch.no_grad():
+        b, vb, _ = m(**inp, hidden=None)
+    assert sorted(a) == sorted(b)
     for k in a:
-        torch.testing.assert_close(a[k], b[k], rtol=0, atol=0)
-    torch.testing.assert_close(va, vb, rtol=0, atol=0)
-    mask = torch.rand(2, 3, 40) > 0.4
-    mask[..., 5] = True
-    torch.testing.assert_close(ref.Policy.masked_softmax(a['target_unit'], mask)[mask],
-                               m.masked_softmax(a['target_unit'], mask)[mask])
+        torch.testing.assert_close(b[k], a[k], rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(vb, torch.from_numpy(gold['value']), rtol=1e-5, atol=1e-6)
+    mask = torch.from_numpy(gold['mask'])
+    torch.testing.assert_close(m.masked_softmax(a['target_unit'], mask)[mask],
+                               torch.from_numpy(gold['masked_softmax'])[mask])
 
 
 def test_fixed_policy_differs_only_in_enemy_tower_pool():
