@@ -11,7 +11,8 @@
 // One 512-thread workgroup (8 waves) per BM-row tile (BM = 48); the BM × P dpre tile never leaves the workgroup between the
 // two products (it is written once to HBM for the pre-RNN weight gradient, and kept in LDS as the second product's
 // A operand):
-// * stage 1, K = 4H in 32-deep slabs, double-buffered through LDS, loads issued RD slabs ahead into a register ring
+// * stage 1, K = 4H in 32-deep slabs, double-buffered through LDS (exact: three buffers, below), loads issued RD
+//   slabs ahead into a register ring
 //   (one slab of lead left every LDS store waiting out a full memory round trip), one barrier per slab; waves as
 //   1 (48 rows) × 8 (32 columns), each 3 × 2 v_mfma_f32_16x16x32_bf16 tiles;
 // * ReLU mask + dpre store in the accumulator layout, dpre written into LDS in the stage-1 A layout (8 slabs);
@@ -28,7 +29,23 @@
 // EXACT = true: exact fp32 on v_mfma_f32_16x16x4_f32 — a 16x16x32 fragment's 8 k values per lane feed 8 chained
 // 16x16x4 MFMAs (call j takes element j: lane l contributes k = 8·(l/16) + j, so the 8 calls cover all 32 k);
 // fp32 LDS rows (144-B pitch), fp32 weights; every launch form (∂X chain, forward chain, heads GEMM + its ∂X
-// product) has an exact instance: the IEEE-fp32 learner.
+// product) has an exact instance: the IEEE-fp32 learner. The exact instances are MFMA-bound (one slab is 48 / 24
+// MFMAs of 32 cycles per wave, two waves per SIMD), so their slab loop keeps the matrix pipe fed across the barrier
+// (profiles/exact_row_kernels.md: ∂X chain 174 → 152 µs, forward chain 171 → 158 µs at the deploy shape):
+// * three rotating LDS buffers per stage instead of two: during the MFMAs of slab k the wave's fragments of slab
+//   k + 1 are already being read into a second register set and slab k + 2 is being stored, so after the barrier the
+//   first MFMA issues at once (with two buffers every wave waited out its ds_read round trip behind each barrier
+//   while the pipe idled: 66 % MFMA-busy on the occupied CUs, 18 % of the wave cycles parked in waits);
+// * the slab stores and the ring's loads are pinned between the MFMAs (sched_group_barrier) — left behind the
+//   last MFMA, in front of the barrier, their drain was exposed once per slab;
+// * the weight slabs are fetched as whole 128-B lines (8 lanes per row piece); one row per lane touched 64 lines
+//   per wave instruction.
+// The fragment reads at the 144-B pitch keep two 2-way bank conflicts per 16-lane group (3.0 conflict cycles per LDS
+// instruction): any odd pitch in 16-B units has them for the b128 lane groups of a (row, k-quarter) fragment, and
+// behind the MFMAs they no longer cost time. Measured and not kept: an 8-deep load ring in stage 2 and the
+// epilogue's mask loads / stage 2's first slab loads issued ahead of the epilogue (within ±1 µs of the above).
+// What remains is CU coverage (234 workgroups on 256 CUs; a persistent grid of 16-row groups ends on the same
+// 3-group critical path) and the per-workgroup prologue / epilogue.
 #include "common.h"
 #include <cstdlib>
 
@@ -52,7 +69,12 @@ struct Lay {
   static constexpr int D = IMG * (P / BK) * A1;            // dpre tile: 8 slabs in the A layout
   static constexpr int B2 = XC * RP;                       // stage-2 B image bytes
   static constexpr int S2 = IMG * B2;
-  static constexpr int BYTES = (2 * S1 > D + 2 * S2) ? 2 * S1 : D + 2 * S2;
+  static constexpr int NB = EXACT ? 3 : 2;                // staging buffers per stage (exact: one being read by
+                                                          // the MFMAs' prefetch, one full, one being written)
+  static constexpr int MAIN = (NB * S1 > D + NB * S2) ? NB * S1 : D + NB * S2;
+  // exact: 16 B per thread past the buffers, where the threads beyond the dG slab's BM rows put their (zero) quad,
+  // so the slab store is branch-free and the whole slab iteration stays one scheduling region
+  static constexpr int BYTES = MAIN + (EXACT ? NT * 16 : 0);
 };
 
 // byte offset of 16-B chunk c of row r in a slab image (bf16: 4 chunks per row, swizzled; fp32: 8, padded rows)
@@ -107,11 +129,11 @@ __device__ __forceinline__ void get_frag(const char* img, int img_bytes, int r, 
 // all NI × NJ tiles of one slab, one product pass at a time over every tile (the three bf16x3 passes of a tile
 // are dependent on its accumulator; interleaving the tiles keeps the MFMA pipe fed instead of waiting out each
 // accumulator's latency twice per tile)
-template <bool EXACT, int NI, int NJ>
+template <bool EXACT, int NI, int NJ, int E0 = 0, int E1 = 8>
 __device__ __forceinline__ void mma_tiles(const Frag (&fa)[NI], const Frag (&fb)[NJ], f32x4 (&acc)[NI][NJ]) {
   if constexpr (EXACT) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e)
+    for (int e = E0; e < E1; ++e)       // (E0 … E1: the caller places other work between two halves of a slab)
 #pragma unroll
       for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -160,8 +182,10 @@ __global__ __launch_bounds__(NT, 1) void dpre_dx_kernel(const float* __restrict_
   const int ar = tid >> 3, ak = (tid & 7) * 4;              // dG slab: one fp32 quad per thread (threads ≥ 8·BM idle)
   const int arow = r0 + ar;
   const int a_off0 = (ar < BM && arow < N) ? (arow * K1 + ak) * 4 : kOob;
-  const int br = tid & 255, bh = tid >> 8;                   // exact W1 slab: 16 k per thread
-  const int b_off0 = (br * K1 + 16 * bh) * ES;
+  // exact W1 slab (256 rows × 128 B): 16-B piece tid & 7 of rows tid / 8 + 64 i, so a wave instruction reads eight
+  // whole 128-B lines (one row per 16 k per thread touched 64 lines per instruction)
+  const int br = tid >> 3, bp = tid & 7;
+  const int b_off0 = (br * K1 + 4 * bp) * ES;
   float4 sa[RD];
   uint4 sb[RD][4];
   // Branch-free: a slab past K reads out of range (zeros, no memory traffic) instead of being skipped — a load
@@ -172,7 +196,7 @@ __global__ __launch_bounds__(NT, 1) void dpre_dx_kernel(const float* __restrict_
     sa[slot] = __builtin_bit_cast(float4, ld16(rA, (in && a_off0 != kOob) ? a_off0 + k0 * 4 : kOob));
     if constexpr (EXACT) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) sb[slot][i] = ld16(rW1h, in ? b_off0 + (k0 + 4 * i) * 4 : kOob);
+      for (int i = 0; i < 4; ++i) sb[slot][i] = ld16(rW1h, in ? b_off0 + (64 * i * K1 + k0) * 4 : kOob);
     } else {
       // slab-major images: the 256 × 32 slab is 16 KB contiguous per image, a wave instruction reads 1 KB of it
       const int o = (k0 / BK) * (P * 64) + tid * 16;
@@ -183,13 +207,13 @@ __global__ __launch_bounds__(NT, 1) void dpre_dx_kernel(const float* __restrict_
       }
     }
   };
-  auto store1 = [&](int slot, int buf) {
-    char* base = lds + buf * L::S1;
+  auto store1 = [&](int slot, int boff) {          // boff: byte offset of the staging buffer
+    char* base = lds + boff;
     char* bb = base + L::IMG * L::A1;
     if constexpr (EXACT) {
-      if (ar < BM) *reinterpret_cast<float4*>(base + ar * L::RP + ak * 4) = sa[slot];
+      *reinterpret_cast<float4*>(lds + (ar < BM ? boff + ar * L::RP + ak * 4 : L::MAIN + tid * 16)) = sa[slot];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(bb + br * L::RP + (16 * bh + 4 * i) * 4) = sb[slot][i];
+      for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(bb + (br + 64 * i) * L::RP + 16 * bp) = sb[slot][i];
     } else {
       uint2 hi, lo;
       split4(sa[slot], hi, lo);
@@ -215,6 +239,50 @@ __global__ __launch_bounds__(NT, 1) void dpre_dx_kernel(const float* __restrict_
   const int nk = K1 / BK;                         // multiple of RD (host check)
 #pragma unroll
   for (int d = 0; d < RD; ++d) load1(d, d * BK);
+  if constexpr (EXACT) {
+    // Three rotating buffers: while the MFMAs of slab ks run, the wave's fragments of slab ks + 1 (stored one
+    // iteration ago) are already on their way from LDS and slab ks + 2 is being stored, so after a barrier the
+    // matrix pipe starts at once instead of waiting out the fragment reads, and the stores sit between the MFMAs
+    int o0 = 0, o1 = L::S1, o2 = 2 * L::S1;        // slab ks, ks + 1, ks + 2
+    store1(0, o0);
+    store1(1, o1);
+    __syncthreads();
+    Frag fa[2][NI1], fb[2][2];
+    auto frags1 = [&](int set, int boff) {
+      const char* base = lds + boff;
+      const char* bb = base + L::A1;
+#pragma unroll
+      for (int i = 0; i < NI1; ++i) get_frag<true>(base, L::A1, i * 16 + r16, q, fa[set][i]);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) get_frag<true>(bb, L::B1, wc * 32 + j * 16 + r16, q, fb[set][j]);
+    };
+    frags1(0, o0);
+    for (int ks0 = 0; ks0 < nk; ks0 += RD) {
+#pragma unroll
+      for (int d = 0; d < RD; ++d) {
+        const int ks = ks0 + d;
+        frags1((d + 1) & 1, o1);                   // (after the last slab: a read nobody uses)
+        mma_tiles<true, NI1, 2, 0, 4>(fa[d & 1], fb[d & 1], acc);
+        store1((d + 2) % RD, o2);                  // slot of slab ks + 2, loaded two iterations ago
+        load1(d, (ks + RD) * BK);                  // slot d held slab ks, stored two iterations ago
+        mma_tiles<true, NI1, 2, 4, 8>(fa[d & 1], fb[d & 1], acc);
+        // issue order: the 10 fragment reads, then one slab store per 8 MFMAs, then the ring's loads; all 48 MFMAs
+        // pinned to their slab (left to itself the compiler put four of the five stores behind the last MFMA, in
+        // front of the barrier, and with only some MFMAs pinned it moved the others across the barriers)
+        __builtin_amdgcn_sched_group_barrier(0x100, 10, 0);
+#pragma unroll
+        for (int g = 0; g < 5; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+          __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x020, 5, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+        __syncthreads();
+        const int t = o0; o0 = o1; o1 = o2; o2 = t;
+      }
+    }
+  } else {
   store1(0, 0);
   __syncthreads();
   for (int ks0 = 0; ks0 < nk; ks0 += RD) {
@@ -229,10 +297,11 @@ __global__ __launch_bounds__(NT, 1) void dpre_dx_kernel(const float* __restrict_
 #pragma unroll
       for (int j = 0; j < 2; ++j) get_frag<EXACT>(bb, L::B1, wc * 32 + j * 16 + r16, q, fb[j]);
       mma_tiles<EXACT, NI1, 2>(fa, fb, acc);
-      store1((d + 1) % RD, (d + 1) & 1);            // (after the last slab: zeros into a buffer nobody reads)
+      store1((d + 1) % RD, ((d + 1) & 1) * L::S1);  // (after the last slab: zeros into a buffer nobody reads)
       load1(d, (ks + RD) * BK);                  // slot d held slab ks, stored at the previous iteration
       __syncthreads();
     }
+  }
   }
 
   // ================= ReLU mask, dpre → HBM and → LDS (stage-2 A operand, 8 slabs in the A layout) =============
@@ -321,25 +390,25 @@ __global__ __launch_bounds__(NT, 1) void dpre_dx_kernel(const float* __restrict_
   char* s2 = lds + L::D;
   constexpr int nk2 = P / BK;
   const int nchunk = X / XC, total = nchunk * nk2;   // multiple of RD (nk2 = 8)
-  const int cr = tid & 127, cq = tid >> 7;        // W2 slab: row, chunk (8 k)
+  const int cr = tid >> 3, cq = tid & 7;          // exact W2 slab (128 rows × 128 B): piece tid & 7 of rows tid / 8, + 64
   uint4 sw[RD][2];
   auto load2 = [&](int slot, int it) {             // branch-free like load1 (it ≥ total: zeros)
     const int c0 = (it / nk2) * XC, kb = it % nk2;
     if constexpr (EXACT) {
-      const int o = it < total ? ((c0 + cr) * P + kb * BK + 8 * cq) * ES : kOob;
+      const int o = it < total ? ((c0 + cr) * P + kb * BK + 4 * cq) * ES : kOob;
       sw[slot][0] = ld16(rW2h, o);
-      sw[slot][1] = ld16(rW2h, o + 16);
+      sw[slot][1] = ld16(rW2h, it < total ? o + 64 * P * ES : kOob);
     } else {                                      // slab-major images: rows c0 … c0+127 of k-block kb, 8 KB
       const int o = it < total ? (kb * X + c0) * 64 + tid * 16 : kOob;
       sw[slot][0] = ld16(rW2h, o);
       sw[slot][1] = ld16(rW2l, o);
     }
   };
-  auto store2 = [&](int slot, int buf) {
-    char* bb = s2 + buf * L::S2;
+  auto store2 = [&](int slot, int boff) {          // boff: byte offset of the staging buffer
+    char* bb = s2 + boff;
     if constexpr (EXACT) {
-      *reinterpret_cast<uint4*>(bb + coff<true>(cr, 2 * cq)) = sw[slot][0];
-      *reinterpret_cast<uint4*>(bb + coff<true>(cr, 2 * cq + 1)) = sw[slot][1];
+      *reinterpret_cast<uint4*>(bb + coff<true>(cr, cq)) = sw[slot][0];
+      *reinterpret_cast<uint4*>(bb + coff<true>(cr + 64, cq)) = sw[slot][1];
     } else {
       const int o = coff<false>(tid >> 2, tid & 3);
       *reinterpret_cast<uint4*>(bb + o) = sw[slot][0];
@@ -353,6 +422,57 @@ __global__ __launch_bounds__(NT, 1) void dpre_dx_kernel(const float* __restrict_
   const __amdgpu_buffer_rsrc_t rDx = rsrc(dx, (long long)N * X * 4);
 #pragma unroll
   for (int d = 0; d < RD; ++d) load2(d, d);
+  auto out2 = [&](int chunk) {                     // a chunk's BM × 128 output tile (rows past N dropped)
+#pragma unroll
+    for (int i = 0; i < NI1; ++i) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int grow = r0 + i * 16 + 4 * q + e;
+        // (through a scalar: __builtin_bit_cast of the vector element itself compiled to element 0 for every e)
+        const float v = acc2[i][0][e];
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rDx,
+                                              grow < N ? (grow * X + chunk * XC + vc * 16 + r16) * 4 : kOob, 0, 0);
+      }
+      acc2[i][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  if constexpr (EXACT) {                          // three rotating W_pre buffers, fragments one slab ahead (stage 1)
+    int o0 = 0, o1 = L::S2, o2 = 2 * L::S2;
+    store2(0, o0);
+    store2(1, o1);
+    __syncthreads();                              // dpre tile and the first two W_pre slabs are in LDS
+    Frag fa[2][NI1], fb[2][1];
+    auto frags2 = [&](int set, int ks, int boff) {
+#pragma unroll
+      for (int i = 0; i < NI1; ++i) get_frag<true>(dimg + ks * L::A1, DIMG, i * 16 + r16, q, fa[set][i]);
+      get_frag<true>(s2 + boff, L::B2, vc * 16 + r16, q, fb[set][0]);
+    };
+    frags2(0, 0, o0);
+    for (int it0 = 0; it0 < total; it0 += RD) {
+#pragma unroll
+      for (int d = 0; d < RD; ++d) {
+        const int it = it0 + d;
+        const int chunk = it / nk2, ks = it % nk2;
+        frags2((d + 1) & 1, (ks + 1) % nk2, o1);
+        mma_tiles<true, NI1, 1, 0, 4>(fa[d & 1], fb[d & 1], acc2);
+        store2((d + 2) % RD, o2);
+        load2(d, it + RD);
+        mma_tiles<true, NI1, 1, 4, 8>(fa[d & 1], fb[d & 1], acc2);
+        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+          __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+        if (ks == nk2 - 1) out2(chunk);
+        __syncthreads();
+        const int t = o0; o0 = o1; o1 = o2; o2 = t;
+      }
+    }
+  } else {
   store2(0, 0);
   __syncthreads();                                // dpre tile and the first W_pre slab are in LDS
   for (int it0 = 0; it0 < total; it0 += RD) {
@@ -366,24 +486,12 @@ __global__ __launch_bounds__(NT, 1) void dpre_dx_kernel(const float* __restrict_
       for (int i = 0; i < NI1; ++i) get_frag<EXACT>(dimg + ks * L::A1, DIMG, i * 16 + r16, q, fa[i]);
       get_frag<EXACT>(bb, L::B2, vc * 16 + r16, q, fb[0]);
       mma_tiles<EXACT, NI1, 1>(fa, fb, acc2);
-      store2((d + 1) % RD, (d + 1) & 1);
+      store2((d + 1) % RD, ((d + 1) & 1) * L::S2);
       load2(d, it + RD);
-      if (ks == nk2 - 1) {                        // chunk done: store its BM × 128 output tile (rows past N dropped)
-#pragma unroll
-        for (int i = 0; i < NI1; ++i) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int grow = r0 + i * 16 + 4 * q + e;
-            // (through a scalar: __builtin_bit_cast of the vector element itself compiled to element 0 for every e)
-            const float v = acc2[i][0][e];
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rDx,
-                                                  grow < N ? (grow * X + chunk * XC + vc * 16 + r16) * 4 : kOob, 0, 0);
-          }
-          acc2[i][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-      }
+      if (ks == nk2 - 1) out2(chunk);             // chunk done
       __syncthreads();
     }
+  }
   }
 }
 

@@ -1121,7 +1121,10 @@ __global__ __launch_bounds__(512, 1) void encoder_fwd_x_kernel(FfParams P) {
     const f32x4 c = x_mma_k128(a, wx);
     // staging of item k + 2 (slot (k - 1) % 3, free in this iteration), loaded at the end of the previous iteration
     // AFTER its emb stores: waiting for it does not wait for stores issued later (vmcnt also counts stores on
-    // gfx950), and the next load is issued after this item's stores for the same reason
+    // gfx950), and the next load is issued after this item's stores for the same reason. (The wait is still a
+    // vmcnt(0) that covers the PREVIOUS item's stores; loading two items ahead into two registers taken in turn made
+    // it a vmcnt(5) that leaves them in flight and changed nothing: 199.2 vs 200.4 µs alone, 181.6 µs in the step
+    // either way, profiles/exact_row_kernels.md — the stores have landed by then.)
     if (wv < 3) stg[(k + 2) % 3][64 * wv + lane] = pre;
     {   // next item's basic tile into the other image (past the range's end: a rewrite nobody reads)
       f32x4 b = x_layer1(stg[(k + 1) % 3], w1x, i, kg);
@@ -1243,30 +1246,28 @@ __global__ __launch_bounds__(256, 2) void encoder_bwd_x2_kernel(FbParams P) {
   for (int t = 0; t < 2; ++t)
     fb_load_build<GIVEN, COMPAT>(bn[t], R, P.ldq, min(k0 + 1, kl), min(k0 + 1, kl) % cnt == 0, cnt, uoff, U, tau,
                                  2 * w + t, i, kg);
-  float l1n[3], ubn[4];
-  auto l1_read = [&](const float* sl) {
+  int buf = 0;
+  for (int k = k0; k < k1; ++k) {
+    lds_barrier();
+    // Order within an item (every value as before, only the order of independent work differs): ∂basic first, then
+    // layer 1 and the ∂W1 / ∂b1 products that need both, so that the staged item's layer-1 operands are read here
+    // instead of being carried from the previous iteration and ∂basic is dead before the next item's build and
+    // prefetch loads; the transposed ∂emb tiles are read behind those, just ahead of their products. With them read
+    // early and the operands carried (≈50 more live registers in the build / prefetch phase) the kernel spilled 14
+    // registers, and a spill reload's vmcnt(0) right behind the prefetch loads of item k + 2 made every item wait
+    // out a full memory round trip.
+    float a[32];
+    x_afrags(img[buf], i, kg, a);                 // ∂emb[row i][e], e = 32s + 8kg + jj (both column tiles)
+    const float* sl = stg[k % 3];                 // (staged two iterations ago)
+    float l1n[3], ub[4];
 #pragma unroll
     for (int cc = 0; cc < 3; ++cc) {
       const int f = 4 * cc + kg;
       l1n[cc] = f < kF ? sl[i * kF + f] : (f == kF ? 1.f : 0.f);
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) ubn[r] = i < kF ? sl[(4 * kg + r) * kF + i] : 0.f;
-  };
-  l1_read(stg[k0 % 3]);
-  int buf = 0;
-  for (int k = k0; k < k1; ++k) {
-    lds_barrier();
-    float a[32];
-    x_afrags(img[buf], i, kg, a);                 // ∂emb[row i][e], e = 32s + 8kg + jj (both column tiles)
-    const float ub[4] = {ubn[0], ubn[1], ubn[2], ubn[3]};
+    for (int r = 0; r < 4; ++r) ub[r] = i < kF ? sl[(4 * kg + r) * kF + i] : 0.f;
     f32x4 bas[2], c[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      bas[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int cc = 0; cc < 3; ++cc) bas[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(l1n[cc], w1x[t][cc], bas[t], 0, 0, 0);
-    }
     {   // ∂basic (before ReLU') of both tiles: the two tiles' chains interleaved (even / odd k summed at the end, as
         // the 8-wave form does)
       f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0, d0 = c0, d1 = c0;
@@ -1283,9 +1284,25 @@ __global__ __launch_bounds__(256, 2) void encoder_bwd_x2_kernel(FbParams P) {
       c[0] = c0 + c1;
       c[1] = d0 + d1;
     }
-    f32x4 et4[8];
 #pragma unroll
-    for (int et = 0; et < 8; ++et) et4[et] = *reinterpret_cast<const f32x4*>(imt[buf] + (16 * et + i) * kXT + 4 * kg);
+    for (int t = 0; t < 2; ++t) {
+      bas[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc) bas[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(l1n[cc], w1x[t][cc], bas[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        bas[t][r] = fmaxf(bas[t][r], 0.f);
+        c[t][r] = bas[t][r] > 0.f ? c[t][r] : 0.f;
+        db1acc[t] += c[t][r];
+      }
+      f32x4 p1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(c[t][r], ub[r], p1, 0, 0, 0);
+      dw1acc[t] += p1;
+    }
     if (w < 3) stg[(k + 2) % 3][64 * w + lane] = pre;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -1294,14 +1311,12 @@ __global__ __launch_bounds__(256, 2) void encoder_bwd_x2_kernel(FbParams P) {
     for (int t = 0; t < 2; ++t)
       fb_load_build<GIVEN, COMPAT>(bn[t], R, P.ldq, min(k + 2, kl), k + 2 <= kl && (k + 2) % cnt == 0, cnt, uoff, U,
                                    tau, 2 * w + t, i, kg);
-    l1_read(stg[(k + 1) % 3]);
     if (w < 3) pre = fb_stage_load(P, min(k + 3, kl), cnt, uoff, w, lane);
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) bas[t][r] = fmaxf(bas[t][r], 0.f);
     // ∂W_τᵀ[j][e] += Σ_rows basic[row][j]·∂emb[row][e], per item from zero then added; the two tiles' chains of an
     // e-tile interleaved
+    f32x4 et4[8];
+#pragma unroll
+    for (int et = 0; et < 8; ++et) et4[et] = *reinterpret_cast<const f32x4*>(imt[buf] + (16 * et + i) * kXT + 4 * kg);
 #pragma unroll
     for (int et = 0; et < 8; ++et) {
       f32x4 p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(bas[0][0], et4[et][0], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
@@ -1313,18 +1328,6 @@ __global__ __launch_bounds__(256, 2) void encoder_bwd_x2_kernel(FbParams P) {
       }
       acc[0][et] += p0;
       acc[1][et] += p1;
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        c[t][r] = bas[t][r] > 0.f ? c[t][r] : 0.f;
-        db1acc[t] += c[t][r];
-      }
-      f32x4 p1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(c[t][r], ub[r], p1, 0, 0, 0);
-      dw1acc[t] += p1;
     }
     buf ^= 1;
   }
