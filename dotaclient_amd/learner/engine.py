@@ -254,13 +254,12 @@ class Learner:
     def _split_mode(self) -> bool:
         """Data-parallel direct step in two phases: the recurrence / pre-RNN / heads gradients are all-reduced on
         the comm stream while the encoder backward still runs (RCCL over xGMI overlapped with backward). The split
-        needs the single-chunk step and a contiguous early-parameter range (DataParallel.split_buckets).
+        needs a contiguous early-parameter range (DataParallel.split_buckets).
         ``DCA_DP_SPLIT=1`` forces it without a process group (single-GPU tests of the two-graph mechanics)."""
         import os
         if getattr(self, '_split', None) is None:
             force = os.environ.get('DCA_DP_SPLIT') == '1'
-            ok = (self.direct() and (self.dp.enabled or force) and self.model.chunks == 1
-                  and os.environ.get('DCA_DP_SPLIT', '') != '0')
+            ok = self.direct() and (self.dp.enabled or force) and os.environ.get('DCA_DP_SPLIT', '') != '0'
             if ok:
                 early = self.model.early_param_names()
                 idx = [i for i, n in enumerate(self.model.param_names) if n in early]

@@ -174,14 +174,6 @@ class FusedPolicy:
                'affine_value.')
         return frozenset(n for n in self.param_names if n.startswith(pre))
 
-    @property
-    def chunks(self) -> int:
-        import os
-        # 1 = no time-chunk overlap: measured on MI355X, work running concurrently on the other XCDs slows the
-        # L2-bound team recurrence by more than it saves (profiles/r5_half_team.md: 5.45 ms at one chunk, 6.2-6.9 ms
-        # chunked)
-        return int(os.environ.get('DCA_PIPELINE_CHUNKS', '1'))
-
     def gate_perm(self, H, device):
         key = (H, str(device))
         if getattr(self, '_perm_key', None) != key:

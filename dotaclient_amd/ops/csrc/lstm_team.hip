@@ -65,7 +65,7 @@ using dca::bf16x8;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kT = 32;                  // workgroups per team (CUs per XCD); VAR bit 4: half teams (16, see below)
+constexpr int kT = 32;                  // workgroups per team (CUs per XCD)
 constexpr int kMaxTeams = 8;
 constexpr int kThreads = 256;
 constexpr int kSc1 = 16;                // buffer cache policy: sc1 (bypass the CU's L1, served by the XCD L2)
@@ -197,20 +197,20 @@ __device__ __forceinline__ bool spin_fail(unsigned& spins, unsigned long long& s
 
 // Team formation + chain queue. Returns the team id (≥ 0) or -1 if this workgroup must exit. Called by all
 // threads; thread 0 does the global traffic, the result is broadcast through LDS.
-__device__ int join_team(TeamCtl* ctl, unsigned* err, int* sh, unsigned* sh_epoch, int ts, bool refuse = false) {
+__device__ int join_team(TeamCtl* ctl, unsigned* err, int* sh, unsigned* sh_epoch, bool refuse = false) {
   if (threadIdx.x == 0) {
     *sh_epoch = ld_acq(&ctl->epoch);
     int res = -1;
     const unsigned x = xcc_id();
     if (x < kMaxTeams && !refuse) {
       const unsigned r = add_agent(&ctl->xcnt[x], 1u);
-      if (r < (unsigned)ts) {
+      if (r < (unsigned)kT) {
         res = (int)x * 64 + (int)r;        // team x, member r
         unsigned spins = 0;
         if (r == 0) {
           bool ok = false;
           while (true) {
-            if (ld_acq(&ctl->xcnt[x]) >= (unsigned)ts) { ok = true; break; }
+            if (ld_acq(&ctl->xcnt[x]) >= (unsigned)kT) { ok = true; break; }
             if (++spins > (1u << 16)) break;
             __builtin_amdgcn_s_sleep(2);
           }
@@ -233,13 +233,13 @@ __device__ int join_team(TeamCtl* ctl, unsigned* err, int* sh, unsigned* sh_epoc
 }
 
 // Next chain for this team (all members agree). Returns chain id or -1 when the queue is drained / aborted.
-__device__ int next_chain(TeamCtl* ctl, int team, int member, unsigned iter, int nch, int* sh, int ts) {
+__device__ int next_chain(TeamCtl* ctl, int team, int member, unsigned iter, int nch, int* sh) {
   if (threadIdx.x == 0) {
     int res = -1;
     unsigned spins = 0;
     if (member == 0) {
       // every member finished the previous chain (its exchange buffers are free again)
-      while (ld_acq(&ctl->done[team]) < (unsigned)ts * iter) {
+      while (ld_acq(&ctl->done[team]) < (unsigned)kT * iter) {
         if (ld_acq(&ctl->abort) || ++spins > (1u << 24)) { spins = ~0u; break; }
         __builtin_amdgcn_s_sleep(1);
       }
@@ -308,8 +308,7 @@ __device__ __forceinline__ void lstm_team_fwd_body(
     TeamCtl* ctl, unsigned* err, int Btot, int Bc, int nch, int S, int sb, int st, unsigned long long* trace,
     int knobs, const float* __restrict__ bias4, const unsigned char* __restrict__ rst) {
   constexpr int H = 128 * KS;
-  constexpr int TS = (VAR & 16) ? 16 : kT;   // workgroups per team
-  constexpr int U = H / TS;             // units per workgroup (4·KS; half teams 8·KS)
+  constexpr int U = H / kT;             // units per workgroup (4·KS)
   constexpr int NTILE = U / 4;          // 16-column MFMA tiles per workgroup (= KS)
   constexpr int KSTEP = H / 32;         // k-steps of the full K
   constexpr int HP = H + 8;             // LDS row pitch (bf16)
@@ -317,7 +316,7 @@ __device__ __forceinline__ void lstm_team_fwd_body(
   constexpr int VV = VAR & 3;                     // variant; VAR & 4: precise (libm-class) activations
   constexpr bool PREC = (VAR & 4) != 0;
   constexpr bool V1 = VV >= 1;
-  constexpr int NT = (VV == 2 || TS == 16) ? 512 : kThreads;    // threads per workgroup (half teams: 8 waves)
+  constexpr int NT = VV == 2 ? 512 : kThreads;    // threads per workgroup
   constexpr int LPU = VV == 2 ? 32 : 16;          // V1/V2: lanes (K slices) per unit
   constexpr int UPW = 64 / LPU;                   // V1/V2: units per wave
   constexpr int KSL = H / LPU;                    // V1/V2: K slice per lane
@@ -325,7 +324,6 @@ __device__ __forceinline__ void lstm_team_fwd_body(
   constexpr int NR = V1 ? R : MT;                 // per-lane row registers (V1: every row; MFMA: one per tile)
   static_assert(!V1 || (F32 && MT == 1), "V1 is the fp32 exact VALU variant");
   static_assert(VV != 2 || H == 512, "V2 maps 8 waves x 2 units onto the 16 units of H = 512");
-  static_assert(TS == kT || (VV == 1 && H == 512), "half teams: the V1 form at H = 512 (8 waves x 4 units)");
   __shared__ short hl[V1 ? 1 : 2][V1 ? 1 : RB][V1 ? 1 : HP];
   __shared__ short hlo[F32 && !V1 ? 2 : 1][F32 && !V1 ? RB : 1][F32 && !V1 ? HP : 1];   // F32: lo bf16 half of h
   // V1: h_{t-1} of each row as 16 K slices, each padded by 4 floats (the 16 lanes of a row read 16 different slices
@@ -337,7 +335,7 @@ __device__ __forceinline__ void lstm_team_fwd_body(
   __shared__ unsigned sh_epoch;
 
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  const int me = join_team(ctl, err, &sh_int, &sh_epoch, TS, (knobs >> 11) & 1);
+  const int me = join_team(ctl, err, &sh_int, &sh_epoch, (knobs >> 11) & 1);
   const unsigned epoch = sh_epoch;
   if (me < 0) return;
   const int team = me >> 6, m = me & 63;
@@ -405,7 +403,7 @@ __device__ __forceinline__ void lstm_team_fwd_body(
   unsigned spins = 0;
   unsigned long long since = 0;
   for (unsigned iter = 0;; ++iter) {
-    const int chain = next_chain(ctl, team, m, iter, nch, &sh_int, TS);
+    const int chain = next_chain(ctl, team, m, iter, nch, &sh_int);
     if (chain < 0) break;
     const int b0 = chain * Bc;
     const int B = min(Bc, Btot - b0);
@@ -697,15 +695,12 @@ __device__ __forceinline__ void lstm_team_bwd_body(
     unsigned long long* trace, short* __restrict__ dg16, float* __restrict__ dbpart, int knobs,
     const unsigned char* __restrict__ rst) {
   constexpr int H = 128 * KS;
-  constexpr int TS = (VAR & 16) ? 16 : kT;   // workgroups per team
-  constexpr int U = H / TS;             // 4·KS units per workgroup (MFMA N, zero-padded to 16; half teams 8·KS)
+  constexpr int U = H / kT;             // 4·KS units per workgroup (MFMA N, zero-padded to 16)
   constexpr int VV = VAR & 3;
   constexpr bool PREC = (VAR & 4) != 0;
   constexpr bool V1 = VV >= 1;
-  constexpr int NWK = VV == 2 ? 8 : 4;  // K parts (waves per 16-unit group)
-  constexpr int UH = V1 && U > 16 ? U / 16 : 1;   // V1 16-unit groups (half teams: 2)
-  constexpr int NW = NWK * UH;          // waves
-  constexpr int NT = 64 * NW;
+  constexpr int NWK = VV == 2 ? 8 : 4;  // K parts = waves
+  constexpr int NT = 64 * NWK;
   constexpr int KW = 4 * H / NWK;       // K (= 4H gate columns) per wave
   constexpr int KSTEP = KW / 32;
   constexpr int RB = MT * 16;
@@ -715,7 +710,6 @@ __device__ __forceinline__ void lstm_team_bwd_body(
   constexpr int NPAIR = ((V1 ? R : RB) * U + NT - 1) / NT;
   static_assert(!V1 || (F32 && MT == 1), "V1 is the fp32 exact VALU variant");
   static_assert(VV != 2 || H == 512, "V2 is the H = 512 variant");
-  static_assert(TS == kT || (VV == 1 && H == 512), "half teams: the V1 form at H = 512 (2 unit groups x 4 K parts)");
   // (Measured and removed in round 5: ∂W_hh accumulated inside this recurrence — 128 accumulators per lane on every
   // step's critical path, 3755 vs 2091 µs for the backward, 7.03 vs 5.59 ms per learner step.)
   __shared__ short dgl[V1 ? 1 : RB][V1 ? 1 : GP];
@@ -724,20 +718,19 @@ __device__ __forceinline__ void lstm_team_bwd_body(
   constexpr int SP = KSL + 4;
   constexpr int DROW = (4 * H / KSL) * SP;   // V1: floats per row image of dG_{t+1}
   __shared__ __attribute__((aligned(16))) float dgf[V1 ? R * DROW : 4];
-  __shared__ float red[NWK][RB][(U > 16 ? U : 16) + 1];
+  __shared__ float red[NWK][RB][16 + 1];
   __shared__ float dbs[RB * U * 4];     // per-(row, unit, gate) bias-gradient sums of a chain
   __shared__ int sh_int;
   __shared__ unsigned sh_epoch;
   // packing: the chain's episode-start flags as a bit image (row b, step t → bit t of rbits[b·wpr + t/32]), built
   // once per chain. Byte loads of the flags at every step — two per owned pair, compared where they were issued —
   // measured +0.32 ms per B = 8, S = 1400 backward call on some boxes (1921 → 2244 µs, scripts/reset_probe.py);
-  // chains with more than kRstWords·32 (row, step) flags read them from global memory as before (so do the half-team
-  // variants, whose LDS is full).
-  constexpr int kRstWords = (VAR & 16) ? 1 : 2048;
+  // chains with more than kRstWords·32 (row, step) flags read them from global memory as before.
+  constexpr int kRstWords = 2048;
   __shared__ unsigned rbits[kRstWords];
 
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  const int me = join_team(ctl, err, &sh_int, &sh_epoch, TS);
+  const int me = join_team(ctl, err, &sh_int, &sh_epoch);
   const unsigned epoch = sh_epoch;
   if (me < 0) return;
   const int team = me >> 6, m = me & 63;
@@ -762,6 +755,8 @@ __device__ __forceinline__ void lstm_team_bwd_body(
   float wq[V1 ? 4 * KSL : 1];
   if constexpr (V1) {
     // lane (ug = lane/16, slice = lane%16): W_hhᵀ of units j0 + 4·ug + uu (uu < 4) over the slice's gate columns
+    // (wv < NWK, so wv / NWK = 0 and wv % NWK = wv here and below: written out because the compiler does not know the
+    // bound, and folding it by hand changed the register allocation of all sixteen V1 backward kernels)
 #pragma unroll
     for (int uu = 0; uu < 4; ++uu) {
       const int unit = 16 * (wv / NWK) + 4 * (lane >> 4) + uu;
@@ -798,7 +793,7 @@ __device__ __forceinline__ void lstm_team_bwd_body(
   unsigned spins = 0;
   unsigned long long since = 0;
   for (unsigned iter = 0;; ++iter) {
-    const int chain = next_chain(ctl, team, m, iter, nch, &sh_int, TS);
+    const int chain = next_chain(ctl, team, m, iter, nch, &sh_int);
     if (chain < 0) break;
     const int b0 = chain * Bc;
     const int B = min(Bc, Btot - b0);
@@ -1040,41 +1035,23 @@ __device__ __forceinline__ void lstm_team_bwd_body(
 #undef TSTAMPB
 }
 
-// Half teams (VAR bit 4): 16 workgroups of 512 threads per team, made CU-EXCLUSIVE by LDS — each workgroup holds
-// ≥ 159 KB of the CU's 160 KB, so no workgroup of another kernel that uses LDS (every GEMM / encoder / chain kernel
-// of the step) can land on a recurrence CU; the other 16 CUs of every XCD stay free for the step's other kernels
-// (which would otherwise co-reside and lengthen every hand-off, profiles/r4_chunk_overlap_probe.md).
-template <int VAR, int PAD>
-__device__ __forceinline__ void claim_cu(int knobs) {
-  if constexpr ((VAR & 16) != 0) {
-    __shared__ char pad[PAD];
-    if (knobs == 0x7fffffff) reinterpret_cast<volatile char*>(pad)[threadIdx.x] = 0;   // (never: keeps the LDS)
-  }
-}
-// pads up to ≈159.5 KB per workgroup: the variants' own LDS (measured from the compiled kernels: forward 4 616 B +
-// 4 608 per extra row, backward 25 864 B + 9 216 per extra row) subtracted from the target
-constexpr int kHalfLds = 163328;
-constexpr int pad_fwd(int var) { return kHalfLds - (4616 + ((1 << ((var >> 5) & 3)) - 1) * 4608); }
-constexpr int pad_bwd(int var) { return kHalfLds - (25864 + ((1 << ((var >> 5) & 3)) - 1) * 9216); }
-inline int team_threads(int var) { return ((var & 3) == 2 || (var & 16)) ? 512 : kThreads; }
-inline int team_size(int var) { return (var & 16) ? 16 : kT; }
+inline int team_threads(int var) { return (var & 3) == 2 ? 512 : kThreads; }
 
 template <int MT, int KS, bool F32, int VAR>
-__global__ __launch_bounds__(((VAR & 3) == 2 || (VAR & 16)) ? 512 : kThreads, 1) void lstm_team_fwd_kernel(
+__global__ __launch_bounds__((VAR & 3) == 2 ? 512 : kThreads, 1) void lstm_team_fwd_kernel(
     const float* __restrict__ xp4, const void* __restrict__ whh, const float* __restrict__ h0,
     const float* __restrict__ c0, short* __restrict__ hs, float* __restrict__ hsf, float* __restrict__ cs,
     float* __restrict__ gates4, float* __restrict__ hn, float* __restrict__ cn, unsigned long long* xg_all,
     TeamCtl* ctl, unsigned* err, int Btot, int Bc, int nch, int S, int sb, int st, unsigned long long* trace,
     int knobs, const float* __restrict__ bias4, const unsigned char* __restrict__ rst) {
   __builtin_amdgcn_s_setprio(3);   // issue priority over co-resident waves of kernels overlapped on other streams
-  claim_cu<VAR, pad_fwd(VAR)>(knobs);
   lstm_team_fwd_body<MT, KS, F32, VAR>(xp4, whh, h0, c0, hs, hsf, cs, gates4, hn, cn, xg_all, ctl, err, Btot, Bc, nch, S, sb,
                              st, trace, knobs, bias4, rst);
   team_exit(ctl, err, nch);
 }
 
 template <int MT, int KS, bool F32, int VAR>
-__global__ __launch_bounds__(((VAR & 3) == 2 || (VAR & 16)) ? 512 : kThreads, 1) void lstm_team_bwd_kernel(
+__global__ __launch_bounds__((VAR & 3) == 2 ? 512 : kThreads, 1) void lstm_team_bwd_kernel(
     const float* __restrict__ dhs, const float* __restrict__ gates4, const float* __restrict__ cs,
     const float* __restrict__ c0, const float* __restrict__ dhn, const float* __restrict__ dcn,
     const void* __restrict__ whh, float* __restrict__ dgates4, float* __restrict__ dh0, float* __restrict__ dc0,
@@ -1082,7 +1059,6 @@ __global__ __launch_bounds__(((VAR & 3) == 2 || (VAR & 16)) ? 512 : kThreads, 1)
     unsigned long long* trace, short* __restrict__ dg16, float* __restrict__ dbpart, int knobs,
     const unsigned char* __restrict__ rst) {
   __builtin_amdgcn_s_setprio(3);
-  claim_cu<VAR, pad_bwd(VAR)>(knobs);
   lstm_team_bwd_body<MT, KS, F32, VAR>(dhs, gates4, cs, c0, dhn, dcn, whh, dgates4, dh0, dc0, xg_all, ctl, err, Btot, Bc, nch,
                              S, sb, st, trace, dg16, dbpart, knobs, rst);
   team_exit(ctl, err, nch);
@@ -1117,7 +1093,7 @@ inline void plan(int B, int& nch, int& Bc, int& MT, int f32 = 0) {
 
 // (F32_, V1_) = (0, 0) bf16 MFMA, (1, 0) bf16x3 MFMA, (1, 1) exact-fp32 VALU for one-row chains
 #define DCA_TEAM_DISPATCH(MT_, KS_, F32_, V1_, ...)                                                        \
-  switch (((V1_) << 12) | ((F32_) << 8) | ((MT_) << 4) | (KS_)) {   /* V1_ bit 4 (half teams) → 0x10000 */                                          \
+  switch (((V1_) << 12) | ((F32_) << 8) | ((MT_) << 4) | (KS_)) {                                          \
     case 0x0011: return __VA_ARGS__(1, 1, false, 0); case 0x0012: return __VA_ARGS__(1, 2, false, 0); \
     case 0x0014: return __VA_ARGS__(1, 4, false, 0); case 0x0021: return __VA_ARGS__(2, 1, false, 0); \
     case 0x0022: return __VA_ARGS__(2, 2, false, 0); case 0x0024: return __VA_ARGS__(2, 4, false, 0); \
@@ -1127,27 +1103,18 @@ inline void plan(int B, int& nch, int& Bc, int& MT, int f32 = 0) {
     case 0x1114: return __VA_ARGS__(1, 4, true, 1);      case 0x2114: return __VA_ARGS__(1, 4, true, 2);      \
     case 0x5111: return __VA_ARGS__(1, 1, true, 5);      case 0x5112: return __VA_ARGS__(1, 2, true, 5);      \
     case 0x5114: return __VA_ARGS__(1, 4, true, 5);      case 0x6114: return __VA_ARGS__(1, 4, true, 6);      \
-    case 0x11114: return __VA_ARGS__(1, 4, true, 17);                                                       \
     case 0x21111: return __VA_ARGS__(1, 1, true, 33);    case 0x21112: return __VA_ARGS__(1, 2, true, 33);   \
     case 0x21114: return __VA_ARGS__(1, 4, true, 33);    case 0x22114: return __VA_ARGS__(1, 4, true, 34);   \
-    case 0x31114: return __VA_ARGS__(1, 4, true, 49);                                                       \
     case 0x41111: return __VA_ARGS__(1, 1, true, 65);    case 0x41112: return __VA_ARGS__(1, 2, true, 65);   \
     case 0x41114: return __VA_ARGS__(1, 4, true, 65);    case 0x42114: return __VA_ARGS__(1, 4, true, 66);   \
-    case 0x51114: return __VA_ARGS__(1, 4, true, 81);                                                       \
     default: return hipErrorInvalidValue;                                                                    \
   }
 
 // fp32 chains of ≤ 4 rows take the exact VALU variant; at H = 512 the backward takes its 8-wave form V2 (measured
 // B=8, S=1400: backward 2069 vs 2137 µs, while the 8-wave forward was SLOWER, 2056 vs 1778 µs).
-// half: the CU-exclusive 16-workgroup teams (V1 form in both directions, H = 512, fast activations).
-inline int use_v1(int f32, int Bc, int H, int backward, int precise, int half = -1) {
-  if (half < 0) {                        // read per launch (two launches per learner step): tests flip it
-    const char* e = getenv("DCA_TEAM_HALF");
-    half = e && e[0] == '1';
-  }
+inline int use_v1(int f32, int Bc, int H, int backward, int precise) {
   if (!(f32 && Bc <= 4)) return 0;
   const int rows = Bc == 1 ? 0 : (Bc == 2 ? 32 : 64);         // VAR bits 5-6: 2 or 4 rows per chain
-  if (half && H == 512 && !precise) return 1 | 16 | rows;
   return ((H == 512 && backward) ? 2 : 1) | (precise ? 4 : 0) | rows;
 }
 
@@ -1186,7 +1153,7 @@ extern "C" hipError_t dca_lstm_team_fwd(const float* xp4, const void* whh, const
   unsigned long long* xg = reinterpret_cast<unsigned long long*>(ws);
   const int KS = H / 128;
 #define DCA_F(mt, ks, f, v)                                                                                     \
-  (lstm_team_fwd_kernel<mt, ks, f, v><<<kMaxTeams * team_size(v), team_threads(v), 0, stream>>>(xp4, whh, h0, c0, hs, hsf, cs, gates4, \
+  (lstm_team_fwd_kernel<mt, ks, f, v><<<kMaxTeams * kT, team_threads(v), 0, stream>>>(xp4, whh, h0, c0, hs, hsf, cs, gates4, \
                                                                           hn, cn, xg, ctl, err, B, Bc, nch, S, sb, \
                                                                           st, trace, team_knobs(), bias4, rst),    \
    hipGetLastError())
@@ -1211,7 +1178,7 @@ extern "C" hipError_t dca_lstm_team_bwd(const float* dhs, const float* gates4, c
   i32x4* xb = reinterpret_cast<i32x4*>(ws);
   const int KS = H / 128;
 #define DCA_B(mt, ks, f, v)                                                                                        \
-  (lstm_team_bwd_kernel<mt, ks, f, v><<<kMaxTeams * team_size(v), team_threads(v), 0, stream>>>(dhs, gates4, cs, c0, dhn, dcn, whh,      \
+  (lstm_team_bwd_kernel<mt, ks, f, v><<<kMaxTeams * kT, team_threads(v), 0, stream>>>(dhs, gates4, cs, c0, dhn, dcn, whh,      \
                                                                           dgates4, dh0, dc0, xb, ctl, err, B, Bc,  \
                                                                           nch, S, sb, st, trace, dg16, dbpart,      \
                                                                           team_knobs(), rst),                      \

@@ -18,14 +18,13 @@ def _rel(a, b):
     return ((a - b).norm() / (b.norm() + 1e-12)).item()
 
 
-@pytest.mark.parametrize('chunks', ['3', '1'])
+# (the ids keep the trailing "-1" they had while the step could also run in time chunks, so the cases keep their names)
 @pytest.mark.parametrize('preset,algo,B,S', [('lstm512', 'ppo', 4, 48), ('lstm128', 'ppo', 7, 33),
                                              ('compat', 'vpg', 3, 40), ('lstm512', 'vpg', 2, 30),
-                                             ('5v5', 'ppo', 3, 24)])
-def test_fused_loss_and_grads_match_reference(gpu_ops, monkeypatch, chunks, preset, algo, B, S):
-    if preset == '5v5' and chunks != '1':
-        pytest.skip('the entity-attention step runs as one time chunk')
-    monkeypatch.setenv('DCA_PIPELINE_CHUNKS', chunks)
+                                             ('5v5', 'ppo', 3, 24)],
+                         ids=['lstm512-ppo-4-48-1', 'lstm128-ppo-7-33-1', 'compat-vpg-3-40-1', 'lstm512-vpg-2-30-1',
+                              '5v5-ppo-3-24-1'])
+def test_fused_loss_and_grads_match_reference(gpu_ops, preset, algo, B, S):
     torch.manual_seed(0)
     cfg = get_config(preset)
     pol = Policy(cfg)
@@ -66,11 +65,10 @@ def test_fused_train_step_decreases_loss(gpu_ops, precision):
     assert losses[-1] < losses[0]
 
 
-@pytest.mark.parametrize('chunks,precision', [('1', 'fp32'), ('3', 'fp32'), ('1', 'fp32-exact'), ('3', 'fp32-exact')])
-def test_graph_captured_step_matches_eager(gpu_ops, monkeypatch, chunks, precision):
+@pytest.mark.parametrize('precision', ['fp32', 'fp32-exact'], ids=['1-fp32', '1-fp32-exact'])   # (ids as before)
+def test_graph_captured_step_matches_eager(gpu_ops, precision):
     """hipGraph-captured forward+backward (Learner.enable_graph) gives the same parameters as eager steps, also
     across host synchronisations between replays (a stale host-staged buffer in the graph would show up there)."""
-    monkeypatch.setenv('DCA_PIPELINE_CHUNKS', chunks)
     torch.manual_seed(0)
     cfg = get_config('lstm512')
     pol = Policy(cfg)
@@ -87,20 +85,44 @@ def test_graph_captured_step_matches_eager(gpu_ops, monkeypatch, chunks, precisi
         torch.cuda.synchronize()
         torch.testing.assert_close(mb['grad_norm'], ma['grad_norm'], rtol=1e-4, atol=1e-7)
     assert b.graph is not None
-    if chunks == '1':
-        torch.testing.assert_close(b.flat.flat, a.flat.flat, rtol=1e-5, atol=1e-6)
-        torch.testing.assert_close(mb['loss'], ma['loss'], rtol=1e-5, atol=1e-6)
-        return
-    # the chunked two-stream fp32 step is not bitwise reproducible run to run (two EAGER learners differed by 4e-8 in
-    # a parameter at step 4; the chunked mode is off by default). Adam's m/√v amplifies such a rounding difference on
-    # a near-zero-gradient element to up to lr per step (seen: 4.7e-5 after 4 steps), and bounds ANY gradient error
-    # the same way — so the parameters are only held to 4 steps × lr, and the decisive check is the last step's
-    # whole gradient: a stale graph buffer is an O(1) relative error there, rounding ≈1e-6
-    torch.testing.assert_close(b.flat.flat, a.flat.flat, rtol=0, atol=4 * lc.learning_rate)
-    assert a.flat.grad.norm() > 0
-    rel = ((b.flat.grad - a.flat.grad).norm() / a.flat.grad.norm()).item()
-    assert rel < 1e-3, rel
-    torch.testing.assert_close(mb['loss'], ma['loss'], rtol=1e-3, atol=1e-5)
+    torch.testing.assert_close(b.flat.flat, a.flat.flat, rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(mb['loss'], ma['loss'], rtol=1e-5, atol=1e-6)
+
+
+@pytest.mark.parametrize('preset,precision,B,S,reset', [
+    ('lstm512', 'fp32-exact', 3, 24, False),        # one-row recurrence chains
+    ('lstm512', 'fp32-exact', 9, 24, False),        # uneven two-row chains
+    ('lstm512', 'fp32', 3, 24, False),
+    ('lstm512', 'fp32-exact', 3, 24, True),         # packed sequences: episode-start flags
+    ('5v5', 'fp32-exact', 2, 16, False)])
+def test_forward_logp_value_equals_the_steps_logp(gpu_ops, monkeypatch, preset, precision, B, S, reset):
+    """``FusedPolicy.forward_logp_value`` (the learner's policy_old evaluation) runs the training step's own forward
+    part: its log-probs are bit-equal to the ones the step returns for the same batch and weights (the second output
+    of ``PipelinedPolicyLoss``, batch-major)."""
+    from dotaclient_amd.models.pipelined import PipelinedPolicyLoss
+    torch.manual_seed(0)
+    cfg = get_config(preset)
+    L = Learner(Policy(cfg), LossConfig(algo='ppo'), device='cuda', backend='fused', dp=False, precision=precision)
+    batch = make_batch(B, S, cfg.layout, cfg.hidden, device='cuda', seed=7)
+    if reset:
+        flags = torch.zeros(B, S, dtype=torch.uint8)
+        flags[0, 0] = flags[0, 9] = flags[1, 5] = flags[2, S - 1] = 1
+        batch['reset'] = flags.cuda()
+    seen = {}
+    apply = PipelinedPolicyLoss.apply
+
+    def spy(*args):
+        out = apply(*args)
+        seen['logp'] = out[1].detach().clone()
+        return out
+    monkeypatch.setattr(PipelinedPolicyLoss, 'apply', staticmethod(spy))
+    L.loss(batch)
+    lp, _ = L.evaluate_sequences(batch, B)
+    torch.cuda.synchronize()
+    L.model.check_error()
+    assert seen['logp'].shape == (B * S,) and lp.shape == (B, S)
+    assert torch.isfinite(lp).all() and float(lp.abs().max()) > 0
+    assert torch.equal(lp.reshape(B * S), seen['logp'])
 
 
 @pytest.mark.parametrize('precision', ['fp32', 'fp32-exact'])
