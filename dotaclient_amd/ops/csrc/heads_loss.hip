@@ -15,6 +15,10 @@
 // before this kernel and passed in `norms`; every row's gradient is then final in one pass.
 //   norms[0] = 1/n_valid  norms[1] = 1/total_selections  norms[2..5] = 1/n_sel[head] (0 if none)
 //   norms[6] = Σ G_last (VPG compat value-bug term)
+//
+// emb is the kernel's HBM traffic (229 MB of fp32 at N = 11 200, U = 40: it ran at HBM speed loading all of it), and
+// most of it cannot reach the result: only units with a target-head mask or action byte set are loaded (on the
+// learner's 1v1 experience 11 % of the (row, unit) pairs, two thirds of the rows none) — see `need` below.
 #include "common.h"
 
 namespace {
@@ -101,24 +105,42 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(Params P) {
     const unsigned char a0 = ar[min(lane, P.A - 1)], a1 = ar[min(lane + 64, P.A - 1)];
     const unsigned char m0 = mr[min(lane, P.A - 1)], m1 = mr[min(lane + 64, P.A - 1)];
     constexpr int kMaxIt = 16;   // U ≤ 64
+    // Units whose embedding can reach the result: a unit enters only through its pointer logit and through
+    // ∂q = Σ ∂tl[u]·emb[u], and with its target-head mask byte and action byte both 0 it has p = 0, ∂tl = ±0 and an
+    // a·logp term of 0 × finite. The action bit is part of `need`, so data with an action outside the mask still reads
+    // its embedding. A row without needed units loads no embedding at all (wave-uniform branch, e8 = 0); elsewhere a
+    // lane whose unit is not needed loads the row's FIRST NEEDED unit instead — lines its neighbours fetch anyway —
+    // so the loads stay unconditional and all in flight. Unneeded units then contribute ±0 to accumulators that start
+    // at +0: dz, dtl, part and logp are bit-identical to loading everything (tests/test_heads_loss_sparse.py).
+    const int un = min(lane, U - 1);
+    const unsigned long long need = __ballot(lane < U && (mr[21 + un] | ar[21 + un]) != 0);
+    const int ufirst = need ? __ffsll((long long)need) - 1 : 0;
     // the row's unit embeddings, 8 features per lane and 4 units per wave-instruction, all loads issued up front
     float e8[kMaxIt][8];
     const int nit = (U + 3) >> 2;
 #pragma unroll
-    for (int it = 0; it < kMaxIt; ++it)
-      if (it < nit) {
-        const size_t o = ((size_t)n * U + min(it * 4 + ug, U - 1)) * kQ + 8 * ks;
-        if constexpr (F32) {
-          const float4 a = *reinterpret_cast<const float4*>(static_cast<const float*>(P.emb) + o);
-          const float4 b = *reinterpret_cast<const float4*>(static_cast<const float*>(P.emb) + o + 4);
-          e8[it][0] = a.x; e8[it][1] = a.y; e8[it][2] = a.z; e8[it][3] = a.w;
-          e8[it][4] = b.x; e8[it][5] = b.y; e8[it][6] = b.z; e8[it][7] = b.w;
-        } else {
-          const dca::bf16x8 h = *reinterpret_cast<const dca::bf16x8*>(static_cast<const short*>(P.emb) + o);
+    for (int it = 0; it < kMaxIt; ++it) {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) e8[it][j] = dca::bf2f(h[j]);
+      for (int j = 0; j < 8; ++j) e8[it][j] = 0.f;
+    }
+    if (need != 0) {
+#pragma unroll
+      for (int it = 0; it < kMaxIt; ++it)
+        if (it < nit) {
+          const int uw = min(it * 4 + ug, U - 1);
+          const size_t o = ((size_t)n * U + (((need >> uw) & 1) ? uw : ufirst)) * kQ + 8 * ks;
+          if constexpr (F32) {
+            const float4 a = *reinterpret_cast<const float4*>(static_cast<const float*>(P.emb) + o);
+            const float4 b = *reinterpret_cast<const float4*>(static_cast<const float*>(P.emb) + o + 4);
+            e8[it][0] = a.x; e8[it][1] = a.y; e8[it][2] = a.z; e8[it][3] = a.w;
+            e8[it][4] = b.x; e8[it][5] = b.y; e8[it][6] = b.z; e8[it][7] = b.w;
+          } else {
+            const dca::bf16x8 h = *reinterpret_cast<const dca::bf16x8*>(static_cast<const short*>(P.emb) + o);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) e8[it][j] = dca::bf2f(h[j]);
+          }
         }
-      }
+    }
     if (lane < 32) s_zl[wv][lane] = zl;
     s_act[wv][lane] = a0; s_act[wv][lane + 64] = a1;
     s_msk[wv][lane] = m0; s_msk[wv][lane + 64] = m1;

@@ -56,6 +56,21 @@
 // Forward store COUNT matters more than bytes: one packed 16-B record {bf16 gates, f32 c, bf16 h} per (row, unit)
 // instead of the three stores ran 1.84 vs 1.895 µs — left out (bf16 saved gates for the backward, and an h unpack
 // pass would eat half the gain).
+// Deferring the V1 forward's output stores (profiles/deferred_output_stores.md; B=8, S=1400, H=512, per forward call,
+// ceiling = no outputs at all: 34-115 µs below the per-step stores depending on the box), two forms, both bitwise
+// equal to the per-step stores and both left out — alone they moved the learner step by 0.026-0.065 ms, every run
+// below every parent run but under three times the parent's run-to-run spread in the same session:
+// (1) register burst: lane `slice` of a unit's 16-lane group latches {c, h, gates} of the step t % 16 == slice and
+// the group stores 16 steps with 3 store instructions behind the 16th publish: 2047 vs 2089 and 2040 vs 2076 µs. The
+// burst's stores cost ≈5× a per-step store each (a wave's instruction scatters over 16 timesteps, 16 B or 64 B per
+// segment), so half of the ceiling stays. (2) an LDS ring of two halves of 32 steps, ds_write behind the publish,
+// a half stored coalesced (64 B of c and h, 256 B of gates per 16 lanes) by all four waves behind the next
+// publish: 2003 vs 2015 and 2001 vs 2008 µs against the per-step form COMPILED INTO THE SAME BINARY — but that
+// binary's per-step form is itself ≈65 µs faster than the parent's identical per-step loop (2008-2015 vs 2076-2089
+// on the same box). Most of what the ring build gains is a side effect of its code / LDS layout (24 KB more LDS,
+// 212 vs 201 VGPRs), not of deferring the stores: an open lead. Backward: dropping its ∂gates store altogether saves
+// 25 µs per call (2086 → 2061 µs, 0.018 µs per step) — less than the call varies between two processes (2086 vs
+// 2132 µs for the same kernel); a deferred form was not built.
 #include "common.h"
 #include <cstdlib>
 
@@ -1065,7 +1080,7 @@ __global__ __launch_bounds__((VAR & 3) == 2 ? 512 : kThreads, 1) void lstm_team_
 }
 
 // DCA_TEAM_KNOBS = pre_sleep | skip_outputs << 8 | probe_first << 9 | xp_step0 << 10 | no poll back-off sleep << 13
-// | three-store forward outputs << 14 (latency experiments only);
+// (latency experiments only; bit 14 once selected a three-store forward output form and is no longer read);
 // DCA_TEAM_FAIL=1 sets bit 11: no workgroup joins a team (fault injection: every chain left unprocessed → err 3);
 // DCA_TEAM_PATIENT=1 sets bit 15: a 60 s instead of 2 s wall-clock hand-off timeout (spin_fail) for runs that share
 // the GPU with another process's persistent kernels (bench.py DCA_SHARED_GPU rehearsals: two ranks' recurrences on
