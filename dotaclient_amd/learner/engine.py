@@ -24,9 +24,7 @@ Batches are dicts of device tensors (see :func:`dotaclient_amd.learner.synthetic
 from __future__ import annotations
 
 import contextlib
-import itertools
 import os
-import threading
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
@@ -34,22 +32,17 @@ import torch
 
 from ..models.policy import Policy
 from ..parallel.dp import DataParallel, FlatParams
+from .graphs import StepGraphs
 from .losses import ppo_loss, split_heads, vpg_loss
 from .optim import FlatAdam
 
 
-# Held while the learner captures a step graph: background threads of the learner process (the ingest stager's
-# rare buffer growth) take it around their pinned / device allocations, so no allocation from another thread lands
-# inside a capture window (HIP invalidates a capture on some cross-thread API calls even in thread-local mode).
-CAPTURE_LOCK = threading.RLock()
-
-
-_GRAPH_TOKENS = itertools.count(1)   # replay-graph cache tokens (Learner._replay_key)
-
-
-def _capture_stream(device):
-    """The graph-capture stream (default priority: high priority measured slower, profiles/r4_stream_priority_ab.txt)."""
-    return torch.cuda.Stream(device=device)
+def _gather_rows(data, fields, idx):
+    """Sequences ``idx`` of the batch-major ``fields`` of ``data`` as time-major rows, plus their ``h0`` / ``c0``:
+    one HIP launch for every field (ops/csrc/glue.hip replay_gather)."""
+    from .. import ops
+    names = list(fields) + [k for k in ('h0', 'c0') if k in data]
+    return dict(zip(names, ops.require().replay_gather([data[k] for k in names], len(fields), idx)))
 
 
 @dataclass
@@ -107,24 +100,26 @@ class Learner:
                 raise ValueError(f'backend fused: no kernel path for {self.policy.config} at {precision}')
         self.counts = self.policy.layout.action_counts()
         self.n_steps = 0
-        self.graph = None                 # captured forward+backward (see enable_graph)
-        self._static_idx: Dict[tuple, torch.Tensor] = {}    # per replay-graph key: its captured index buffer
+        self.graphs = StepGraphs(self.device)     # captured steps (see enable_graph)
         self._graph_warmup = 0
+        self._split: Optional[bool] = None        # two-phase DP step; decided on first use (_split_mode)
+        self._err_any: Optional[torch.Tensor] = None    # sticky DP-wide error flag, made by the first DP sync
 
     def enable_graph(self, warmup: int = 2):
-        """Capture forward + loss + backward of the fused step in a hipGraph after ``warmup`` eager steps. The
-        step launches a few hundred kernels (per-chunk GEMMs, the persistent recurrence, fused kernels); eager
-        Python + hipBLASLt launch cost is several ms per step, a graph replay is one launch. The DP all-reduce and
-        the fused Adam stay outside the graph (RCCL collectives are not captured). Inputs are copied into
-        static buffers before each replay; the batch shapes must not change."""
-        if self.backend != 'fused' or self.device.type != 'cuda':
-            return False
-        # only the forward-computed step (models/pipelined.py) is captured: it has no work in an autograd
-        # backward thread (capturing _PolicyLoss's autograd backward gave wrong gradients on replay)
-        if not self.model.use_pipeline():
+        """Capture forward + loss + backward of the direct fused step in a hipGraph after ``warmup`` eager steps.
+        The step is a few dozen hand-written kernels (no vendor GEMM) on several streams; a replay spares the
+        Python and launch cost of each of them. The DP all-reduce and the fused Adam stay outside the graph (RCCL
+        collectives are not captured). Inputs are copied into the static buffers of their key (learner/graphs.py)
+        before each replay."""
+        if not self.direct():       # only the autograd-free step is captured: it has no work in a backward thread
             return False
         self._graph_warmup = max(1, int(warmup))
         return True
+
+    @property
+    def graph(self):
+        """The most recently captured step graph (None before any capture and once its step was released)."""
+        return self.graphs.last
 
     # ------------------------------------------------------------------------------------------------
     def _autocast(self):
@@ -231,17 +226,9 @@ class Learner:
         over the pool viewed as (capacity·S, …) — no batch-major copy, no transpose."""
         B = idx.numel()
         fields = self.STEP_FIELDS + tuple(k for k in ('reset', 'vt') if k in replay.data)
-        if idx.is_cuda:                 # one HIP launch for every field (ops/csrc/glue.hip replay_gather)
-            from .. import ops
-            seq = [k for k in ('h0', 'c0') if k in replay.data]
-            outs = ops.require().replay_gather([replay.data[k] for k in fields] +
-                                               [replay.data[k] for k in seq], len(fields),
-                                               idx.contiguous())
-            return dict(zip(list(fields) + seq, outs))
-        ar = getattr(self, '_arange', None)
-        if ar is None or ar.numel() < S or ar.device != idx.device:
-            ar = self._arange = torch.arange(max(S, 1), device=idx.device, dtype=torch.long)
-        rows = (idx.view(1, B) * S + ar[:S].view(S, 1)).reshape(-1)
+        if idx.is_cuda:
+            return _gather_rows(replay.data, fields, idx.contiguous())
+        rows = (idx.view(1, B) * S + torch.arange(S, device=idx.device, dtype=torch.long).view(S, 1)).reshape(-1)
         out = {}
         for k in fields:
             pool = replay.data[k]
@@ -256,8 +243,7 @@ class Learner:
         the comm stream while the encoder backward still runs (RCCL over xGMI overlapped with backward). The split
         needs a contiguous early-parameter range (DataParallel.split_buckets).
         ``DCA_DP_SPLIT=1`` forces it without a process group (single-GPU tests of the two-graph mechanics)."""
-        import os
-        if getattr(self, '_split', None) is None:
+        if self._split is None:
             force = os.environ.get('DCA_DP_SPLIT') == '1'
             ok = self.direct() and (self.dp.enabled or force) and os.environ.get('DCA_DP_SPLIT', '') != '0'
             if ok:
@@ -288,132 +274,38 @@ class Learner:
     def _graph_ready(self) -> bool:
         return bool(self._graph_warmup) and self.n_steps >= self._graph_warmup
 
-    @staticmethod
-    def _capture_mode() -> str:
-        """Only this thread's HIP calls are capture-checked ('thread_local'): other threads of the process keep
-        running while the learner captures — RCCL's watchdog querying events, or an in-process actor stepping its
-        own graphs on its own streams (learner/e2e.py). Neither touches the capturing stream."""
-        return 'thread_local'
-
-    def _replay_split(self, key, body):
-        """Split-mode capture/replay: ``body(hook)`` is captured as TWO graphs — the hook, called once by the step
-        at its split point, ends the first capture and begins the second (same memory pool). Replay: graph 1, then
-        the early buckets' all-reduce on the comm stream, then graph 2 overlapping it."""
-        graphs = self.__dict__.setdefault('_graphs', {})
-        if key not in graphs:
-            if getattr(self, '_graph_stream', None) is None:
-                self._graph_stream = _capture_stream(self.device)
-            s = self._graph_stream
-            cur = torch.cuda.current_stream(self.device)
-            s.wait_stream(cur)
-            with torch.cuda.stream(s):              # eager warm-up on the capture stream, no collectives
-                body(lambda: None)
-            cur.wait_stream(s)
-            mode = self._capture_mode()
-            g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            switched = []
-
-            def switch():
-                g1.capture_end()
-                g2.capture_begin(pool=g1.pool(), capture_error_mode=mode)
-                switched.append(True)
-
-            torch.cuda.synchronize(self.device)
-            with CAPTURE_LOCK, torch.cuda.stream(s):
-                g1.capture_begin(capture_error_mode=mode)
-                out = body(switch)
-                if not switched:
-                    raise RuntimeError('direct step never reached its DP split point')
-                g2.capture_end()
-            cur.wait_stream(s)
-            graphs[key] = ((g1, g2), out)
-            self.graph = g1
-        (g1, g2), out = graphs[key]
-        g1.replay()
-        self.dp.launch_early()
-        g2.replay()
-        return out
-
-    def _replay_graph(self, key, body):
-        """Capture ``body`` (a function of the static inputs) once per key, then replay it."""
-        graphs = self.__dict__.setdefault('_graphs', {})
-        if key not in graphs:
-            # the capture stream must outlive the graph: hipBLASLt's per-stream workspace that the captured GEMM
-            # nodes point at belongs to it
-            if getattr(self, '_graph_stream', None) is None:
-                self._graph_stream = _capture_stream(self.device)
-            s = self._graph_stream
-            cur = torch.cuda.current_stream(self.device)
-            s.wait_stream(cur)
-            with torch.cuda.stream(s):          # one more eager run on the capture stream (allocator warm-up)
-                body()
-            cur.wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with CAPTURE_LOCK, torch.cuda.graph(g, stream=s, capture_error_mode=self._capture_mode()):
-                out = body()
-            graphs[key] = (g, out)
-            self.graph = g
-        g, out = graphs[key]
-        g.replay()
-        return out
+    def _captured(self, key, make_static, fill, rows):
+        """The captured direct step of ``key`` (learner/graphs.py): ``make_static()`` makes a new key's static inputs,
+        ``fill(static)`` writes this step's into a known key's, ``rows(static)`` → (time-major rows, B, S). The one
+        place that decides between the single graph and the split pair around ``dp.launch_early``."""
+        split = self._split_mode()
+        return self.graphs.step(key, make_static, fill,
+                                lambda static, hook: self._direct_body(*rows(static), hook=hook if split else None),
+                                between=self.dp.launch_early if split else None)
 
     def _step_direct_batch(self, batch):
         if not self._graph_ready():
-            bt, B, S = self.batch_to_time_major(batch)
-            return self._direct_body(bt, B, S)
+            return self._direct_body(*self.batch_to_time_major(batch))
         B, S = batch['env'].shape[:2]
-        key = ('batch', B, S, tuple(sorted(batch)))
-        if key not in self.__dict__.get('_graphs', {}):
-            self._static_in = {k: v.clone() for k, v in batch.items()}
-        else:
+
+        def fill(static):
             for k, v in batch.items():
-                self._static_in[k].copy_(v, non_blocking=True)
-
-        if self._split_mode():
-            def body_split(hook):
-                bt, B_, S_ = self.batch_to_time_major(self._static_in)
-                return self._direct_body(bt, B_, S_, hook=hook)
-            return self._replay_split(key, body_split)
-
-        def body():
-            bt, B_, S_ = self.batch_to_time_major(self._static_in)
-            return self._direct_body(bt, B_, S_)
-        return self._replay_graph(key, body)
-
-    @staticmethod
-    def _replay_key(replay, B: int, S: int):
-        """Graph-cache key of a replay source. A token unique for the object's lifetime, never ``id()``: a later pool
-        allocated at a freed pool's address must not find (and replay) a graph wired to the freed storage."""
-        tok = replay.__dict__.get('_dca_graph_token')
-        if tok is None:
-            tok = replay.__dict__['_dca_graph_token'] = next(_GRAPH_TOKENS)
-        return ('replay', tok, B, S)
+                static[k].copy_(v, non_blocking=True)
+        return self._captured(('batch', B, S, tuple(sorted(batch))), lambda: {k: v.clone() for k, v in batch.items()},
+                              fill, self.batch_to_time_major)
 
     def release_graphs(self, replay) -> int:
-        """Drop every captured step (and its private memory pool + static index buffer) bound to ``replay`` — call
-        before its storage is reallocated or freed. Returns the number of graphs released."""
-        tok = replay.__dict__.get('_dca_graph_token')
-        if tok is None:
-            return 0
-        graphs = self.__dict__.get('_graphs', {})
-        dead = [k for k in graphs if k[0] == 'replay' and k[1] == tok]
-        for k in dead:
-            g = graphs.pop(k)[0]
-            if self.graph is g or (isinstance(g, tuple) and self.graph in g):
-                self.graph = None
-            self._static_idx.pop(k, None)
-        return len(dead)
+        """Drop every captured step bound to ``replay`` — call before its storage is reallocated or freed. Returns
+        the number of steps released."""
+        return self.graphs.release(replay)
 
     def train_step_replay(self, replay, B: int, recent: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """One DP optimizer step on a minibatch sampled from an on-device replay (``learner.replay.HbmReplay``).
-        On the direct fused path the gather itself is part of the captured graph (only the sampled indices are
-        copied in)."""
+        On the direct fused path the gather itself is part of the captured graph: the sampled positions go straight
+        into the graph's own index buffer (one copy)."""
         if self.direct() and self._graph_ready() and getattr(replay, 'host_sampling', False):
-            key = self._replay_key(replay, B, replay.S)
-            if key in self.__dict__.get('_graphs', {}):
-                # captured step: the sampled positions go straight into the graph's own index buffer (one copy)
-                replay.sample_into(self._static_idx[key], recent)
-                return self._step_replay_key(replay, key, None)
+            return self._step_replay_key(replay, B, lambda: replay.sample_indices(B, recent),
+                                         lambda static: replay.sample_into(static, recent))
         return self.train_step_indices(replay, replay.sample_indices(B, recent))
 
     def train_step_indices(self, replay, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -423,24 +315,15 @@ class Learner:
         if not self.direct():
             return self.train_step(replay.gather(idx))
         if self._graph_ready():
-            return self._step_replay_key(replay, self._replay_key(replay, idx.numel(), replay.S), idx)
+            return self._step_replay_key(replay, idx.numel(), lambda: idx, lambda static: static.copy_(idx))
         return self._finish(self._direct_body(self.gather_time_major(replay, idx, replay.S), idx.numel(), replay.S))
 
-    def _step_replay_key(self, replay, key, idx: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
-        """Captured replay step of graph ``key``; every key owns its static index buffer (``idx`` None: already
-        written into it)."""
-        B, S = key[2], key[3]
-        if key not in self.__dict__.get('_graphs', {}):
-            self._static_idx[key] = idx.clone()
-        elif idx is not None:
-            self._static_idx[key].copy_(idx)
-        sidx = self._static_idx[key]
-        if self._split_mode():
-            vec = self._replay_split(key, lambda hook: self._direct_body(
-                self.gather_time_major(replay, sidx, S), B, S, hook=hook))
-        else:
-            vec = self._replay_graph(key, lambda: self._direct_body(self.gather_time_major(replay, sidx, S), B, S))
-        return self._finish(vec)
+    def _step_replay_key(self, replay, B: int, indices, fill) -> Dict[str, torch.Tensor]:
+        """Captured step on ``B`` sequences of ``replay``: the key's static input is its index buffer, a copy of
+        ``indices()`` when the key is new and written by ``fill`` from then on."""
+        S = replay.S
+        return self._finish(self._captured(self.graphs.replay_key(replay, B, S), lambda: indices().clone(), fill,
+                                           lambda sidx: (self.gather_time_major(replay, sidx, S), B, S)))
 
     def _sync_and_step(self):
         """DP reduction + optimizer step. With the fused Adam on a multi-rank job the has-grad average is taken
@@ -455,7 +338,7 @@ class Learner:
         if self.backend == 'fused' and self.dp.enabled:
             # the reduced flag is non-zero on EVERY rank when any rank's recurrence failed: keep it sticky so that
             # all ranks raise together at the iteration boundary (check_error), not only the failing one
-            sticky = getattr(self, '_err_any', None)
+            sticky = self._err_any
             if sticky is None:
                 sticky = self._err_any = torch.zeros_like(self.dp.err_flag)
             torch.maximum(sticky, self.dp.err_flag, out=sticky)
@@ -467,7 +350,7 @@ class Learner:
         self.opt.check_nonfinite()
         if self.backend != 'fused':
             return
-        sticky = getattr(self, '_err_any', None)
+        sticky = self._err_any
         if sticky is not None and float(sticky.item()) != 0.0:
             own = int(self.model.err.item())
             sticky.zero_()
@@ -481,7 +364,7 @@ class Learner:
         non-zero it calls :meth:`check_error`, whose host syncs then only happen on the failure path."""
         flags = [self.opt.nonfinite]
         if self.backend == 'fused':
-            sticky = getattr(self, '_err_any', None)
+            sticky = self._err_any
             if sticky is not None:
                 flags.append(sticky)
             flags.append(self.model.err)
@@ -516,16 +399,11 @@ class Learner:
         eager module."""
         S = data['units'].shape[1]
         if self.direct():
-            from .. import ops
-            C = ops.require()
             fields = ('units', 'env', 'actions', 'masks') + (('reset',) if 'reset' in data else ())
-            seq = [k for k in ('h0', 'c0') if k in data]
             lps, vals = [], []
             for i0 in range(0, n, chunk):
                 i1 = min(n, i0 + chunk)
-                idx = torch.arange(i0, i1, device=self.device, dtype=torch.int64)
-                outs = C.replay_gather([data[k] for k in fields] + [data[k] for k in seq], len(fields), idx)
-                bt = dict(zip(list(fields) + seq, outs))
+                bt = _gather_rows(data, fields, torch.arange(i0, i1, device=self.device, dtype=torch.int64))
                 lp, v = self.model.forward_logp_value(bt, i1 - i0, S)
                 lps.append(lp.view(S, i1 - i0).t())
                 vals.append(v.view(S, i1 - i0).t())

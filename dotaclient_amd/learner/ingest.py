@@ -344,8 +344,8 @@ class IngestPipeline:
                 # learner may be capturing its step graph right now, and a device-wide sync from this thread would
                 # invalidate that capture
                 slot.consumed.synchronize()
-            # pinned / device allocations are serialised against the learner's graph captures (learner/engine.py)
-            from .engine import CAPTURE_LOCK
+            # pinned / device allocations are serialised against the learner's graph captures (learner/graphs.py)
+            from .graphs import CAPTURE_LOCK
             with CAPTURE_LOCK:
                 slot.host = torch.empty(cap, dtype=torch.uint8, pin_memory=self.cuda)
                 if self.cuda:

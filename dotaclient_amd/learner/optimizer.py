@@ -1139,7 +1139,7 @@ class DotaOptimizer:
 
     def _publish_snapshot(self, snap, meta, ev, version: int):
         import io
-        from .engine import CAPTURE_LOCK
+        from .graphs import CAPTURE_LOCK
         # the device → host copies (and the release of the device snapshot) stay out of a step-graph capture window
         with CAPTURE_LOCK:
             st = getattr(self, '_pub_stream', None)

@@ -428,7 +428,7 @@ def _backward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], f: For
         main.wait_stream(sL)
         # DP split point: every gradient of the recurrence, pre-RNN and heads is final here (the big ones are
         # already in the flat buffer); apply the small ones and let the learner all-reduce those buckets while
-        # the encoder backward below runs (see Learner._replay_split)
+        # the encoder backward below runs (see learner/graphs.py: the hook cuts the capture in two)
         if not lin:
             grads['rnn.bias_ih_l0'] = db         # (gate-major already: the kernel writes PyTorch's order)
             grads['rnn.bias_hh_l0'] = db

@@ -313,9 +313,9 @@ def test_iteration_pool_growth_releases_captured_graphs(gpu_ops):
         data = make_batch(cap, S, cfg.layout, cfg.hidden, device='cuda', seed=seed)
         fields = {k: v for k, v in data.items() if k in Learner.STEP_FIELDS + ('h0', 'c0')}
         if pool is not None:
-            n_before = len(b._graphs)
+            n_before = len(b.graphs)
             assert b.release_graphs(pool) >= 1
-            assert len(b._graphs) < n_before
+            assert len(b.graphs) < n_before
         pool = _IterationPool(fields, cap, S)
         for k in fields:
             pool.data[k].copy_(fields[k])
@@ -326,8 +326,39 @@ def test_iteration_pool_growth_releases_captured_graphs(gpu_ops):
             torch.cuda.synchronize()
             torch.testing.assert_close(mb['loss'], ma['loss'], rtol=1e-5, atol=1e-7, msg=f'cap {cap} step {step}')
         torch.testing.assert_close(b.flat.flat, a.flat.flat, rtol=1e-5, atol=1e-6)
-    keys = [k for k in b._graphs if k[0] == 'replay']
-    assert len(keys) == 1 and set(b._static_idx) == set(keys)
+    keys = [k for k in b.graphs if k[0] == 'replay']
+    index_owners = {k for k in b.graphs if isinstance(b.graphs.static(k), torch.Tensor)}
+    assert len(keys) == 1 and index_owners == set(keys)
+
+
+def test_graph_cache_keeps_static_inputs_per_key(gpu_ops):
+    """Captured batch steps of two shapes, interleaved (A, A, B, A, B): every key replays over its own static inputs,
+    so a step of shape A after B's capture still equals the eager step (one shared input set would be rebound to
+    B's buffers by B's capture, and A's next batch copied into them)."""
+    torch.manual_seed(0)
+    cfg = get_config('lstm128')
+    pol = Policy(cfg)
+    ref = copy.deepcopy(pol)
+    lc = LossConfig(algo='ppo')
+    a = Learner(pol, lc, device='cuda', backend='fused', dp=False)
+    b = Learner(ref, lc, device='cuda', backend='fused', dp=False)
+    assert b.enable_graph(warmup=1)
+    shapes = {'A': (3, 24), 'B': (4, 24)}
+    for seed, name in enumerate('AABAB'):
+        bt = make_batch(*shapes[name], cfg.layout, cfg.hidden, device='cuda', seed=seed)
+        ma = a.train_step(bt)
+        mb = b.train_step(bt)
+        torch.cuda.synchronize()
+        torch.testing.assert_close(mb['grad_norm'], ma['grad_norm'], rtol=1e-4, atol=1e-7, msg=f'step {seed} {name}')
+        torch.testing.assert_close(mb['loss'], ma['loss'], rtol=1e-5, atol=1e-6, msg=f'step {seed} {name}')
+    torch.testing.assert_close(b.flat.flat, a.flat.flat, rtol=1e-5, atol=1e-6)
+    keys = [k for k in b.graphs if k[0] == 'batch']
+    assert sorted(k[1:3] for k in keys) == sorted(shapes.values())
+    statics = [b.graphs.static(k) for k in keys]
+    assert len(keys) == 2 and statics[0] is not statics[1]
+    for k, st in zip(keys, statics):
+        assert tuple(st['env'].shape[:2]) == k[1:3]
+    assert not {v.data_ptr() for v in statics[0].values()} & {v.data_ptr() for v in statics[1].values()}
 
 
 def test_bf16_learner_has_no_fused_branch():
