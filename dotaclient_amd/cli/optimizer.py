@@ -78,6 +78,17 @@ def build_parser():
     ap.add_argument('--replay-gb', type=float, default=0.0, help='on-HBM replay buffer budget in GB (0 = off)')
     ap.add_argument('--replay-capacity', type=int, default=0, help='replay capacity in sequences (overrides GB)')
     ap.add_argument('--replay-recent', type=int, default=0, help='sample from the newest N sequences (0 = all)')
+    ap.add_argument('--replay-sampler', type=str, default='uniform', choices=['uniform', 'mixture'],
+                    help='uniform over the ring / its newest N, or a mixture of the newest N and a prioritised draw '
+                         'over the whole ring (priorities from the in-step V-trace advantages)')
+    ap.add_argument('--replay-recent-frac', type=float, default=0.5,
+                    help='mixture sampler: share of the draws taken from the --replay-recent newest sequences')
+    ap.add_argument('--replay-priority-alpha', type=float, default=0.6,
+                    help='mixture sampler: priority exponent (0 = uniform over the filled ring)')
+    ap.add_argument('--replay-priority-eta', type=float, default=0.9,
+                    help='mixture sampler: weight of max|A| against mean|A| in a sequence\'s priority')
+    ap.add_argument('--replay-ratio', type=float, default=1.0,
+                    help='replay steps per iteration as a multiple (>= 1) of epochs x fresh minibatches')
     ap.add_argument('--prefetch-rollouts', type=int, default=0,
                     help='decode up to N experience messages ahead on a background thread (0 = inline)')
     ap.add_argument('--allow-pickle-experience', type=str2bool, default=False,
@@ -112,6 +123,9 @@ def main(argv=None):
                           precision=args.precision, graph=bool(args.graph), async_checkpoint=bool(args.async_checkpoint),
                           checkpoint_keep=args.checkpoint_keep, replay_gb=args.replay_gb,
                           replay_capacity=args.replay_capacity, replay_recent=args.replay_recent,
+                          replay_sampler=args.replay_sampler, replay_recent_frac=args.replay_recent_frac,
+                          replay_priority_alpha=args.replay_priority_alpha,
+                          replay_priority_eta=args.replay_priority_eta, replay_ratio=args.replay_ratio,
                           allow_pickle_experience=args.allow_pickle_experience,
                           prefetch_rollouts=args.prefetch_rollouts, pack_sequences=args.pack_sequences)
     broker = make_broker(args.broker or f'tcp://{args.ip}:{args.port}')

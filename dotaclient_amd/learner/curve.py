@@ -37,7 +37,9 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
                        replay_gb: float = 0.0, snapshot_lags=(120.0, 300.0, 600.0), snapshot_games: int = 64,
                        old_logp: str = 'actor', league_matrix_n: int = 0,
                        advantages: str = 'vtrace-step', weight_lag: int = 0,
-                       replay_recent: int = 0) -> List[Dict]:
+                       replay_recent: int = 0, replay_sampler: str = 'uniform', replay_recent_frac: float = 0.5,
+                       replay_priority_alpha: float = 0.6, replay_priority_eta: float = 0.9,
+                       replay_ratio: float = 1.0) -> List[Dict]:
     """Train for ``budget`` seconds (evaluations excluded) and return the evaluation rows (the first one before
     any training). ``on_row`` is called with every row as it is produced; ``save_model``: path that receives the
     final weights (a reference-format state_dict file). ``eval_precision``: the validation games' policy step.
@@ -50,7 +52,10 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
     weights against sampled past versions (``latest_weights_prob`` of the games self-play the latest), the actor's
     policy step runs at ``actor_precision`` ('fp8' for config 5), and ``replay_gb`` > 0 trains every minibatch from
     an on-HBM replay of that size (learner/replay.py) instead of the iteration's fresh rollouts — uniformly over the
-    whole buffer, or over its ``replay_recent`` newest sequences."""
+    whole buffer, or over its ``replay_recent`` newest sequences; ``replay_sampler='mixture'`` draws a share
+    ``replay_recent_frac`` from those newest and the rest by priority over the whole ring (``replay_priority_alpha`` /
+    ``replay_priority_eta``, ops/replay.py), ``replay_ratio`` > 1 runs that many times more replay steps per
+    iteration."""
     import json
     import os
 
@@ -76,7 +81,10 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
                           run_local=True,
                           xp_timeout=300.0, histogram_freq=10 ** 9, async_checkpoint=True, prefetch_rollouts=64,
                           pack_sequences=bool(pack), seed=seed, replay_gb=replay_gb, old_logp=old_logp,
-                          replay_recent=int(replay_recent),
+                          replay_recent=int(replay_recent), replay_sampler=replay_sampler,
+                          replay_recent_frac=float(replay_recent_frac),
+                          replay_priority_alpha=float(replay_priority_alpha),
+                          replay_priority_eta=float(replay_priority_eta), replay_ratio=float(replay_ratio),
                           advantages=advantages)
     opt = DotaOptimizer(cfg, broker)
     ws = WeightStore(model, device='cpu')
@@ -170,6 +178,9 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
             evaluate({'t_train': 0.0, 'iteration': 0, 'samples': 0, 'actor_steps': 0, 'model': model,
                       'precision': precision, 'backend': backend, 'pack': bool(pack), 'league': league,
                       'actor_precision': actor_precision, 'replay_gb': replay_gb, 'replay_recent': int(replay_recent),
+                      'replay_sampler': replay_sampler, 'replay_recent_frac': float(replay_recent_frac),
+                      'replay_priority_alpha': float(replay_priority_alpha),
+                      'replay_priority_eta': float(replay_priority_eta), 'replay_ratio': float(replay_ratio),
                       'advantages': advantages, 'old_logp': old_logp, 'weight_lag': int(weight_lag)})
         th.start()
         next_eval = (int(trained // eval_every) + 1) * eval_every

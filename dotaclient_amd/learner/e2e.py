@@ -316,7 +316,10 @@ def measure_e2e_node(model: str = 'lstm512', device='cuda', duration: float = 20
                      report=None, record_consumed: int = 0, progress=None, pack: bool = False,
                      league: Optional[str] = None, latest_weights_prob: float = 1.0, actor_precision: str = 'bf16',
                      replay_gb: float = 0.0, actor_procs: int = 1, replay_prefill: bool = False,
-                     old_logp: str = 'actor', advantages: str = 'vtrace-step') -> Dict[str, float]:
+                     old_logp: str = 'actor', advantages: str = 'vtrace-step', replay_recent: int = 0,
+                     replay_sampler: str = 'uniform', replay_recent_frac: float = 0.5,
+                     replay_priority_alpha: float = 0.6, replay_priority_eta: float = 0.9,
+                     replay_ratio: float = 1.0) -> Dict[str, float]:
     """The reference's node topology end to end (optimizer.py:144-150, 274-287; ks-app/components/optimizer.jsonnet:
     79-174): ONE experience queue per node fed by actor processes, ``WORLD_SIZE`` learner ranks (one per GPU, DDP
     over RCCL) consuming disjoint rollouts from it as competing consumers, and rank 0 alone checkpointing and
@@ -335,7 +338,9 @@ def measure_e2e_node(model: str = 'lstm512', device='cuda', duration: float = 20
 
     BASELINE config 5 (``league='pfsp'``, ``actor_precision='fp8'``, ``replay_gb`` > 0): the actors play a PFSP
     self-play league on the fp8 policy step and every learner trains from an on-HBM replay of ``replay_gb`` GB
-    (learner/replay.py) instead of the iteration's fresh rollouts only.
+    (learner/replay.py) instead of the iteration's fresh rollouts only — sampled uniformly (over the ring or its
+    ``replay_recent`` newest), or with ``replay_sampler='mixture'`` a share ``replay_recent_frac`` from those newest
+    and the rest by priority (ops/replay.py); ``replay_ratio`` > 1 multiplies the replay steps per iteration.
 
     ``actor_procs`` > 1 splits each rank's ``games`` and ``threads`` over that many actor processes (each with its own
     interpreter, GIL and graphs on the rank's GPU): the actor loop's Python between its native parallel regions is
@@ -445,7 +450,10 @@ def measure_e2e_node(model: str = 'lstm512', device='cuda', duration: float = 20
                               histogram_freq=10 ** 9, async_checkpoint=dev.type == 'cuda',
                               prefetch_rollouts=prefetch, record_consumed=record_consumed, pack_sequences=pack,
                               replay_gb=replay_gb, replay_prefill=replay_prefill, old_logp=old_logp,
-                              advantages=advantages)
+                              advantages=advantages, replay_recent=int(replay_recent),
+                              replay_sampler=replay_sampler, replay_recent_frac=float(replay_recent_frac),
+                              replay_priority_alpha=float(replay_priority_alpha),
+                              replay_priority_eta=float(replay_priority_eta), replay_ratio=float(replay_ratio))
         opt = DotaOptimizer(cfg, broker, checkpoint=rank == 0)     # rank 0 publishes model version 0
         say(f'e2e: learner ready ({transport} broker {addr}); waiting for the actor process')
         t_ready = time.time() + 900
@@ -564,7 +572,10 @@ def measure_e2e_node(model: str = 'lstm512', device='cuda', duration: float = 20
                          replay_sequences=(len(opt.replay) if opt is not None and opt.replay is not None else 0),
                          replay_capacity=(opt.replay.capacity if opt is not None and opt.replay is not None else 0),
                          replay_fill=(opt.replay.fill_fraction if opt is not None and opt.replay is not None else 0.),
-                         replay_prefill=replay_prefill,
+                         replay_prefill=replay_prefill, replay_recent=int(replay_recent),
+                         replay_sampler=replay_sampler, replay_recent_frac=float(replay_recent_frac),
+                         replay_priority_alpha=float(replay_priority_alpha),
+                         replay_priority_eta=float(replay_priority_eta), replay_ratio=float(replay_ratio),
                          # PPO advantages (in-step V-trace / per-iteration policy_old forward / actor GAE — whatever
                          # they cost is inside every rate above) and the PPO ratio's denominator
                          advantages=advantages, old_logp=old_logp)

@@ -172,6 +172,11 @@ class Learner:
                                        tm(batch['vt']).cpu(), B, S, cfg.gamma, cfg.gae_lambda, cfg.vtrace_rho_bar,
                                        cfg.vtrace_c_bar)
             dev = batch['env'].device
+            pc = getattr(self, '_priority_cfg', None)
+            if pc is not None:      # the step trains from a prioritised replay (_step_prioritized)
+                from ..ops.replay import priority_from_advantages
+                self._seq_priority = torch.stack(priority_from_advantages(adv, tm(batch['vt'])[:, 2].cpu(), B, S,
+                                                                          *pc)).to(dev)
             back = (lambda x: x.reshape(S, B).t().contiguous().to(dev))
             adv, ret = back(adv), back(ret)
             v = batch['vt'][..., 2].float()
@@ -303,10 +308,56 @@ class Learner:
         """One DP optimizer step on a minibatch sampled from an on-device replay (``learner.replay.HbmReplay``).
         On the direct fused path the gather itself is part of the captured graph: the sampled positions go straight
         into the graph's own index buffer (one copy)."""
+        if getattr(replay, 'prioritized', False):
+            return self._step_prioritized(replay, B, recent)
         if self.direct() and self._graph_ready() and getattr(replay, 'host_sampling', False):
             return self._step_replay_key(replay, B, lambda: replay.sample_indices(B, recent),
                                          lambda static: replay.sample_into(static, recent))
         return self.train_step_indices(replay, replay.sample_indices(B, recent))
+
+    def _step_prioritized(self, replay, B: int, recent: Optional[int]) -> Dict[str, torch.Tensor]:
+        """A step from a prioritised replay: the replay's sampler fills the index buffer (the captured step's static
+        one: the mixture sampler is a kernel writing straight into it, ``host_sampling`` does not apply), the step
+        computes the sampled sequences' new priorities from its un-normalised V-trace advantages (fused: the
+        ``seq_priority`` kernel inside the step, next to the V-trace kernel; torch: ops/replay.py
+        ``priority_from_advantages``) and a scatter stores them behind the step, in stream order. The sampler's
+        statistics of this step ride in the returned metrics. Eager and captured steps draw the same index stream."""
+        update = self.cfg.vtrace and self.cfg.algo == 'ppo'
+        if not update and replay.priority_alpha > 0:
+            raise ValueError("a prioritised replay with priority_alpha > 0 needs the in-step V-trace advantages: "
+                             "LossConfig(algo='ppo', vtrace=True) (learner/optimizer.py advantages='vtrace-step')")
+        fused = self.backend == 'fused'
+        # (alpha = 0 without the in-step V-trace: every priority stays at its entry value 1 = (·)^0, nothing to store)
+        pc = (replay.priority_eta, replay.priority_alpha, replay.priority_eps) if update else None
+        self._priority_cfg = pc
+        if fused:
+            self.model.priority_cfg = pc
+        try:
+            if self.direct() and self._graph_ready():
+                if replay.sampler == 'mixture' or getattr(replay, 'host_sampling', False):
+                    fill = (lambda static: replay.sample_into(static, recent))
+                else:
+                    fill = (lambda static: static.copy_(replay.sample_indices(B, recent)))
+                m = self._step_replay_key(replay, B, lambda: replay.sample_indices(B, recent), fill)
+                idx = self.graphs.static(self.graphs.replay_key(replay, B, replay.S))
+            else:
+                idx = replay.sample_indices(B, recent)
+                if self.direct():
+                    m = self._finish(self._direct_body(self.gather_time_major(replay, idx, replay.S), B, replay.S))
+                else:
+                    m = self.train_step(replay.gather(idx))
+        finally:
+            self._priority_cfg = None
+            if fused:
+                self.model.priority_cfg = None
+        if update:
+            # fused: the buffer the step's seq_priority kernel wrote (models/pipelined.py _heads_loss) — the very
+            # tensor a captured step is wired to, looked up, never re-made
+            replay.update_priorities(idx, self.model._scratch[f'seq_priority_{B}'] if fused else self._seq_priority)
+        st = replay.sampler_state.stats.clone()     # one copy: the values below are views of it
+        m['replay/recent_draws'], m['replay/age_sum'], m['replay/priority_sum'] = st[0], st[1], st[2]
+        m['replay/priority_max'] = st[3]
+        return m
 
     def train_step_indices(self, replay, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
         """One DP optimizer step on the pool sequences ``idx`` (device int64) of ``replay`` — any object with

@@ -79,6 +79,18 @@ class OptimizerConfig:
     replay_capacity: int = 0           # sequences (overrides replay_gb)
     replay_recent: int = 0             # sample from the newest N sequences (0 = whole buffer)
     replay_prefill: bool = False       # fill the ring to capacity from the first ingest (benchmarks, HbmReplay.prefill)
+    # 'uniform' (over the ring or its replay_recent newest) | 'mixture': a share replay_recent_frac of the draws from
+    # the replay_recent newest sequences, the rest proportional to the per-sequence priority
+    # (eta·max|A| + (1 − eta)·mean|A| + eps)^alpha of the in-step V-trace advantages A (ops/replay.py; needs
+    # advantages='vtrace-step' and PPO when alpha > 0)
+    replay_sampler: str = 'uniform'
+    replay_recent_frac: float = 0.5
+    replay_priority_alpha: float = 0.6
+    replay_priority_eta: float = 0.9
+    replay_priority_eps: float = 1e-3
+    # replay steps per iteration = ratio × epochs × (fresh sequences // batch_size), the fractional remainder carried
+    # to the next iteration (at least one step per iteration); 1.0 = as often as fresh data arrives
+    replay_ratio: float = 1.0
     ingest: str = 'auto'               # 'device' (HIP return/GAE scan over the uploaded rollouts) | 'host' | 'auto'
     artifact_url: Optional[str] = None  # off-node mirror of checkpoints + events (reference: GCS bucket, §utils.artifacts)
     allow_pickle_experience: bool = False  # accept reference-agent pickles (restricted unpickler); off: DCX1 only
@@ -200,6 +212,18 @@ class DotaOptimizer:
                       ('device' if (cfg.device == 'auto' and torch.cuda.is_available()) or
                        str(cfg.device).startswith('cuda') else 'host'))
         self.vtrace_step = cfg.advantages == 'vtrace-step' and cfg.algo == 'ppo' and dev_ingest == 'device'
+        if cfg.replay_sampler not in ('uniform', 'mixture'):
+            raise ValueError(f"replay_sampler must be 'uniform' or 'mixture', got {cfg.replay_sampler!r}")
+        if cfg.replay_ratio < 1.0:
+            raise ValueError(f'replay_ratio must be >= 1 (got {cfg.replay_ratio}): the replay is read at least as '
+                             'often as fresh data arrives')
+        if cfg.replay_sampler == 'mixture' and not replay_on:
+            raise ValueError("replay_sampler='mixture' needs a replay (replay_capacity or replay_gb)")
+        if cfg.replay_sampler == 'mixture' and cfg.replay_priority_alpha > 0 and not self.vtrace_step:
+            raise ValueError("replay_sampler='mixture' with replay_priority_alpha > 0 takes its priorities from the "
+                             "in-step V-trace advantages: it needs advantages='vtrace-step' (on the device ingest) and "
+                             f"algo='ppo' (got advantages={cfg.advantages!r}, algo={cfg.algo!r}, ingest {dev_ingest})")
+        self._replay_carry = 0.0           # fractional replay steps owed to the next iteration (replay_ratio)
         lc = LossConfig(algo=cfg.algo, learning_rate=cfg.learning_rate, entropy_coef=cfg.entropy_coef,
                         vf_coef=cfg.vf_coef, clip_eps=cfg.clip_eps, gamma=cfg.gamma, gae_lambda=cfg.gae_lambda,
                         max_grad_norm=cfg.max_grad_norm, compat_value_bug=cfg.compat_value_bug,
@@ -267,11 +291,15 @@ class DotaOptimizer:
                     logger.warning('replay_gb %.0f > %.0f GB free on %s: the replay takes %.0f GB', gb, free,
                                    self.device, fit)
                     gb = fit
+            prio = cfg.replay_sampler == 'mixture'
             cap = cfg.replay_capacity or HbmReplay.capacity_for_bytes(gb * 1e9, cfg.seq_len,
                                                                        self.policy_cfg.layout, hid, pk,
-                                                                       vtrace=self.vtrace_step)
+                                                                       vtrace=self.vtrace_step, prioritized=prio)
+            kw = dict(prioritized=True, sampler='mixture', recent_frac=cfg.replay_recent_frac,
+                      priority_alpha=cfg.replay_priority_alpha, priority_eta=cfg.replay_priority_eta,
+                      priority_eps=cfg.replay_priority_eps) if prio else {}
             self.replay = HbmReplay(cap, cfg.seq_len, self.policy_cfg.layout, hid, self.device, seed=cfg.seed,
-                                    reset=pk, vtrace=self.vtrace_step)
+                                    reset=pk, vtrace=self.vtrace_step, **kw)
             logger.info('on-device replay: %d sequences, %.2f GB', cap, self.replay.nbytes / 1e9)
         self.time_last_step = time.time()
         if self.iteration_start == 1:
@@ -829,11 +857,20 @@ class DotaOptimizer:
             self.replay.add(data, version=it)
             if cfg.replay_prefill and self.replay.fill_fraction < 1.0:
                 self.replay.prefill()
-            for _ in range(cfg.epochs * (n // cfg.batch_size)):
+            n_replay = cfg.epochs * (n // cfg.batch_size)
+            if cfg.replay_ratio != 1.0:
+                # replay_ratio × the fresh-data count, the fraction carried over so the long-run ratio is exact
+                want = cfg.replay_ratio * n_replay + self._replay_carry
+                n_replay = max(1, int(want + 1e-9))
+                self._replay_carry = max(0.0, want - n_replay)
+            for _ in range(n_replay):
                 m = self.learner.train_step_replay(self.replay, cfg.batch_size, cfg.replay_recent or None)
                 losses.append(m['loss'])
                 for k, v in m.items():
                     metrics_acc.setdefault(k, []).append(v)
+            if getattr(self.replay, 'prioritized', False):
+                # (one value per iteration: the running count of non-finite priorities)
+                metrics_acc['replay/priority_nonfinite'] = [self.replay.priority_nonfinite.clone()]
         pool = self._iteration_pool(data, n) if (self.replay is None and self.learner.direct()) else None
         for ep in range(cfg.epochs if self.replay is None else 0):
             perm = torch.randperm(n, generator=g)
@@ -900,6 +937,7 @@ class DotaOptimizer:
         pending = dict(it=it, losses=losses, metrics_acc=metrics_acc, ema_snap=ema_snap, n_seq=n_seq,
                        subrewards=subrewards, rollout_lens=rollout_lens, weight_ages=weight_ages, canvas=canvas,
                        done=done, ev=(ev_t0, ev_t1), n_train=len(losses), published=published,
+                       n_fresh=cfg.epochs * (n // cfg.batch_size),
                        n_rollouts=len(rollouts), host=host)
         self.timer.stop('train')
         if defer:
@@ -1025,6 +1063,16 @@ class DotaOptimizer:
                 metrics[k] = mean[k]
         if self.replay is not None:
             metrics['replay/size'] = float(len(self.replay))
+            if 'replay/priority_sum' in mean:
+                # the sampler's device statistics of every step (Learner._step_prioritized), per draw
+                B = float(cfg.batch_size)
+                metrics['replay/priority_mean'] = mean['replay/priority_sum'] / B
+                metrics['replay/priority_max'] = mean['replay/priority_max']
+                metrics['replay/sample_age'] = mean['replay/age_sum'] / B
+                metrics['replay/recent_draw_frac'] = mean['replay/recent_draws'] / B
+                metrics['replay/priority_nonfinite'] = mean['replay/priority_nonfinite']
+            if 'replay/priority_sum' in mean or cfg.replay_ratio != 1.0:
+                metrics['replay/ratio'] = p['n_train'] / max(1, p.get('n_fresh', 0))
         for team, v in self.running.mean.items():
             metrics[f'rewards/running_mean_{team}'] = v
         for team, v in self.running.std.items():

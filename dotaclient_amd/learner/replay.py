@@ -10,7 +10,12 @@ per field on the GPU (``(capacity, seq_len, …)``), so
 * capacity is chosen from a byte budget (``capacity_for_bytes``): one LSTM-512 1v1 sequence of 1400 steps is
   ≈2.4 MB, so 200 GB holds ≈80k sequences (≈115 M timesteps).
 
-Sampling is uniform over the filled part, optionally restricted to the ``recent`` newest sequences. Off-policy
+Sampling is uniform over the filled part, optionally restricted to the ``recent`` newest sequences
+(``sampler='uniform'``), or — on a ``prioritized`` ring — a mixture (``sampler='mixture'``, ops/replay.py): a share
+``recent_frac`` of the draws uniform over the ``recent`` newest sequences, the rest proportional to a per-sequence
+priority over the whole ring. The priority ``(eta·max|A| + (1 − eta)·mean|A| + eps)^alpha`` comes from the in-step
+V-trace advantages of the step that last trained on the sequence (``update_priorities``); new sequences enter at the
+current maximum. Sampler, priorities and their statistics live on the replay's device: no host sync per step. Off-policy
 correction: the PPO ratio against the stored behaviour ``logp_old``, and — with the in-step V-trace (``vtrace``,
 learner/optimizer.py advantages='vtrace-step') — every sampled sequence's advantages and value targets recomputed
 at the weights being trained, with truncated importance weights against that behaviour log-prob.
@@ -46,21 +51,31 @@ def field_specs(S: int, layout: UnitLayout, hidden: Optional[int], reset: bool =
 
 
 def bytes_per_sequence(S: int, layout: UnitLayout, hidden: Optional[int], reset: bool = False,
-                       vtrace: bool = False) -> int:
+                       vtrace: bool = False, prioritized: bool = False) -> int:
     n = 0
     for shape, dt in field_specs(S, layout, hidden, reset, vtrace).values():
         k = 1
         for d in shape:
             k *= d
         n += k * torch.tensor([], dtype=dt).element_size()
-    return n + 8     # version
+    return n + 8 + (4 if prioritized else 0)     # version (+ the fp32 priority of a prioritised ring)
 
 
 class HbmReplay:
     def __init__(self, capacity: int, S: int, layout: UnitLayout, hidden: Optional[int], device, seed: int = 0,
-                 reset: bool = False, vtrace: bool = False):
+                 reset: bool = False, vtrace: bool = False, prioritized: bool = False, sampler: str = 'uniform',
+                 recent_frac: float = 0.5, priority_alpha: float = 0.6, priority_eta: float = 0.9,
+                 priority_eps: float = 1e-3):
         if capacity < 1:
             raise ValueError('replay capacity must be >= 1')
+        if sampler not in ('uniform', 'mixture'):
+            raise ValueError(f"sampler must be 'uniform' or 'mixture', got {sampler!r}")
+        if sampler == 'mixture' and not prioritized:
+            raise ValueError("sampler='mixture' needs prioritized=True (the per-sequence priority vector)")
+        if not 0.0 <= recent_frac <= 1.0:
+            raise ValueError(f'recent_frac must lie in [0, 1], got {recent_frac}')
+        if priority_alpha < 0 or not 0.0 <= priority_eta <= 1.0 or priority_eps <= 0:
+            raise ValueError('priority_alpha >= 0, 0 <= priority_eta <= 1 and priority_eps > 0 are required')
         self.capacity = int(capacity)
         self.S = S
         self.device = torch.device(device)
@@ -76,15 +91,28 @@ class HbmReplay:
         # sample_indices (the device generator); off by default so sample_indices' stream of indices stays the one
         # the learner uses (tests replay it)
         self.host_sampling = False
+        self.prioritized = bool(prioritized)
+        self.sampler = sampler
+        self.recent_frac = float(recent_frac)
+        self.priority_alpha, self.priority_eta = float(priority_alpha), float(priority_eta)
+        self.priority_eps = float(priority_eps)
+        self.current_version = 0        # newest version added: the sampler's age statistic counts from it
+        if self.prioritized:
+            from ..ops.replay import SamplerState
+            # one fp32 priority per slot (0 = unfilled): a separate attribute, not a field the learner step gathers
+            self.priority = torch.zeros(self.capacity, dtype=_F32, device=self.device)
+            self.priority_nonfinite = torch.zeros(1, dtype=_F32, device=self.device)    # non-finite p_raw so far
+            self.sampler_state = SamplerState(self.capacity, self.device, seed)
 
     @staticmethod
     def capacity_for_bytes(budget: float, S: int, layout: UnitLayout, hidden: Optional[int], reset: bool = False,
-                           vtrace: bool = False) -> int:
-        return max(1, int(budget // bytes_per_sequence(S, layout, hidden, reset, vtrace)))
+                           vtrace: bool = False, prioritized: bool = False) -> int:
+        return max(1, int(budget // bytes_per_sequence(S, layout, hidden, reset, vtrace, prioritized)))
 
     @property
     def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self.data.values()) + self.version.numel() * 8
+        n = sum(t.numel() * t.element_size() for t in self.data.values()) + self.version.numel() * 8
+        return n + (self.priority.numel() * 4 if self.prioritized else 0)
 
     def __len__(self):
         return self.size
@@ -113,6 +141,11 @@ class HbmReplay:
                 dst[d0:d0 + cnt].copy_(src[s0:s0 + cnt], non_blocking=True)
         for d0, _, cnt in spans:
             self.version[d0:d0 + cnt] = int(version)
+            if self.prioritized:
+                # new rows enter at the maximum priority the last sampling pass found (1.0 before any): a device
+                # scalar broadcast into the slice, no host sync
+                self.priority[d0:d0 + cnt] = self.sampler_state.max_priority
+        self.current_version = max(self.current_version, int(version))
         self.cursor = (self.cursor + n) % self.capacity
         self.size = min(self.capacity, self.size + n)
         self.inserted += n
@@ -135,6 +168,8 @@ class HbmReplay:
             for v in self.data.values():
                 v[have:have + n].copy_(v[:n])
             self.version[have:have + n] = -1
+            if self.prioritized:
+                self.priority[have:have + n].copy_(self.priority[:n])
             have += n
             wrote += n
         self.size = self.capacity
@@ -151,6 +186,8 @@ class HbmReplay:
     def sample_indices(self, B: int, recent: Optional[int] = None) -> torch.Tensor:
         if self.size == 0:
             raise RuntimeError('replay is empty')
+        if self.sampler == 'mixture':
+            return self._sample_mixture(torch.empty(B, dtype=torch.long, device=self.device), recent)
         m = self._window(recent)
         r = torch.randint(0, m, (B,), device=self.device, generator=self._g)
         # newest-first window ending at the cursor: position (cursor - 1 - r) mod capacity
@@ -163,6 +200,8 @@ class HbmReplay:
         slots form a ring; a slot is refilled only after its previous copy has run."""
         if self.size == 0:
             raise RuntimeError('replay is empty')
+        if self.sampler == 'mixture':
+            return self._sample_mixture(out, recent)
         B = out.numel()
         if out.device.type != 'cuda':
             out.copy_(self.sample_indices(B, recent))
@@ -182,6 +221,33 @@ class HbmReplay:
         ev = slot[1] = slot[1] or torch.cuda.Event()
         ev.record()
         return out
+
+    def _sample_mixture(self, out: torch.Tensor, recent: Optional[int] = None, u_out=None) -> torch.Tensor:
+        """The mixture sampler (ops/replay.py) into ``out`` (int64 on the replay's device — a captured step's static
+        index buffer, or a fresh tensor): on the GPU two launches reading the priorities where they are, the draw
+        counter kept on the device; on the CPU the float64 reference fed from this replay's generator. Leaves the
+        pass's maximum priority and statistics in ``sampler_state``."""
+        from ..ops import replay as R
+        st = self.sampler_state
+        if self.device.type == 'cuda':
+            return R.sample_mixture(self.priority, self.version, st, out, self.size, self.cursor, recent,
+                                    self.recent_frac, self.current_version, u_out)
+        u = torch.rand(out.numel(), 2, generator=self._g)
+        if u_out is not None:
+            u_out.copy_(u)
+        idx, stats = R.sample_mixture_reference(self.priority, self.size, self.cursor, self.capacity, recent,
+                                                self.recent_frac, u, self.version, self.current_version)
+        st.max_priority.fill_(float(self.priority.max()))
+        st.stats[:3].copy_(stats)
+        st.stats[3] = float(st.max_priority)
+        st.counter += 1
+        return out.copy_(idx)
+
+    def update_priorities(self, idx: torch.Tensor, pf: torch.Tensor):
+        """Store the priorities ``pf[0]`` of the sequences ``idx`` a step just trained on (``pf`` (2, B) f32: P and the
+        non-finite flags, ops/replay.py) — in stream order, no sync, no allocation on the GPU."""
+        from ..ops.replay import scatter_priorities
+        scatter_priorities(self.priority, idx, pf.to(self.device), self.priority_nonfinite)
 
     def gather(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
         return {k: v.index_select(0, idx) for k, v in self.data.items()}

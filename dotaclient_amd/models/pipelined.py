@@ -328,6 +328,12 @@ def _heads_loss(fp, W: Dict[str, torch.Tensor], f: Forward, act_t, msk_t, adv_t,
         adv_v, ret_t, fp.vtrace_stats = vtrace_step(None, lp_a, lpo_t, vt_t, B, S, lc.gamma, lc.gae_lambda,
                                                     getattr(lc, 'vtrace_rho_bar', 1.0),
                                                     getattr(lc, 'vtrace_c_bar', 1.0), z=f.z, vcol=149)
+        pc = getattr(fp, 'priority_cfg', None)
+        if pc is not None:
+            # the step trains from a prioritised replay (learner/engine.py): the sequences' new priorities from the
+            # un-normalised advantages, into the policy's persistent (2, B) buffer (ops/csrc/replay_sample.hip)
+            from ..ops.replay import seq_priority
+            seq_priority(adv_v, vt_t.contiguous(), fp.scratch(f'seq_priority_{B}', (2, B), torch.float32, f.z.device), B, S, *pc)
         adv_t = torch.empty_like(adv_v)
         C.adv_normalize(adv_v, vt_t[:, 2].contiguous(), adv_t, float(EPS))
     dz, dtl, part, logp = C.heads_loss(f.z, f.emb, act_t, msk_t, adv_t, ret_t, lpo_t, nret_t, norms, algo,

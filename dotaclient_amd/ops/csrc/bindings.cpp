@@ -1116,6 +1116,63 @@ std::vector<torch::Tensor> replay_gather(std::vector<torch::Tensor> pools, int64
   return out;
 }
 
+// Prioritised mixture sampler (replay_sample.hip): priority (capacity) f32, version (capacity) i64, the sampler's
+// device state (block sums / maxima, draw counter), out (B) i64 = the caller's index buffer; writes max_priority (1),
+// stats (4) f64 {newest-window draws, Σ version lag, Σ P[idx], max P} and, if given, the uniforms u_out (B, 2).
+void replay_sample(torch::Tensor priority, torch::Tensor version, torch::Tensor block_sum, torch::Tensor block_max,
+                   torch::Tensor counter, int64_t seed, torch::Tensor out, torch::Tensor max_priority,
+                   torch::Tensor stats, c10::optional<torch::Tensor> u_out, int64_t size, int64_t cursor, int64_t m,
+                   double recent_frac, int64_t current_version) {
+  CHECK_F32(priority); CHECK_F32(block_max); CHECK_F32(max_priority);
+  CHECK_DEV(version); CHECK_CONTIG(version); CHECK_DT(version, at::kLong);
+  CHECK_DEV(counter); CHECK_CONTIG(counter); CHECK_DT(counter, at::kLong);
+  CHECK_DEV(out); CHECK_CONTIG(out); CHECK_DT(out, at::kLong);
+  CHECK_DEV(block_sum); CHECK_CONTIG(block_sum); CHECK_DT(block_sum, at::kDouble);
+  CHECK_DEV(stats); CHECK_CONTIG(stats); CHECK_DT(stats, at::kDouble);
+  const int64_t cap = priority.numel(), B = out.numel();
+  const int64_t nblk = (cap + 4095) / 4096;
+  TORCH_CHECK(cap >= 1 && cap <= (1 << 20), "replay_sample: 1..2^20 slots");
+  TORCH_CHECK(version.numel() == cap, "replay_sample: one version per slot");
+  TORCH_CHECK(block_sum.numel() >= nblk && block_max.numel() >= nblk, "replay_sample: block scratch too small");
+  TORCH_CHECK(counter.numel() >= 1 && max_priority.numel() >= 1 && stats.numel() >= 4, "replay_sample: state sizes");
+  TORCH_CHECK(B >= 1 && B <= (1 << 16), "replay_sample: 1..65536 draws");
+  TORCH_CHECK(size >= 1 && size <= cap && m >= 1 && m <= size && cursor >= 0 && cursor < cap,
+              "replay_sample: ring state out of range");
+  float* u = nullptr;
+  if (u_out.has_value() && u_out->defined()) {
+    CHECK_F32((*u_out));
+    TORCH_CHECK(u_out->numel() == 2 * B, "replay_sample: u_out must be (B, 2)");
+    u = ptr<float>(*u_out);
+  }
+  hip_check(dca_replay_sample(ptr<float>(priority), ptr<long long>(version), ptr<double>(block_sum),
+                              ptr<float>(block_max), (int)cap, (int)size, (int)cursor, (int)m, (float)recent_frac,
+                              (long long)current_version, (unsigned long long)seed, ptr<long long>(counter),
+                              ptr<long long>(out), (int)B, ptr<float>(max_priority), ptr<double>(stats), u,
+                              cur_stream()), "dca_replay_sample");
+}
+
+// Per-sequence priorities of a time-major minibatch (replay_sample.hip seq_priority_kernel): adv (B·S), vt (B·S, 4),
+// out (2, B) = (P, non-finite flag).
+void seq_priority(torch::Tensor adv, torch::Tensor vt, torch::Tensor out, int64_t B, int64_t S, double eta,
+                  double alpha, double eps) {
+  CHECK_F32(adv); CHECK_F32(vt); CHECK_F32(out);
+  TORCH_CHECK(B >= 1 && S >= 1 && adv.numel() == B * S && vt.numel() == 4 * B * S && out.numel() == 2 * B,
+              "seq_priority: adv (B·S), vt (B·S, 4), out (2, B)");
+  hip_check(dca_seq_priority(ptr<float>(adv), ptr<float>(vt), ptr<float>(out), (int)B, (int)S, (float)eta,
+                             (float)alpha, (float)eps, cur_stream()), "dca_seq_priority");
+}
+
+// priority[idx[b]] = pf[0, b]; nonfinite[0] += Σ pf[1, :] (indices outside the ring are skipped)
+void priority_scatter(torch::Tensor priority, torch::Tensor idx, torch::Tensor pf, torch::Tensor nonfinite) {
+  CHECK_F32(priority); CHECK_F32(pf); CHECK_F32(nonfinite);
+  CHECK_DEV(idx); CHECK_CONTIG(idx); CHECK_DT(idx, at::kLong);
+  const int64_t B = idx.numel();
+  TORCH_CHECK(pf.numel() == 2 * B && nonfinite.numel() >= 1 && priority.numel() < (int64_t(1) << 31),
+              "priority_scatter: pf (2, B), nonfinite (1)");
+  hip_check(dca_priority_scatter(ptr<float>(priority), (int)priority.numel(), ptr<long long>(idx), ptr<float>(pf),
+                                 (int)B, ptr<float>(nonfinite), cur_stream()), "dca_priority_scatter");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1202,6 +1259,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "[K/32][R][32] images, the dpre_dx operand layout)", py::arg("src"), py::arg("slab_major") = false);
   m.def("enc_small_grads", &enc_small_grads, "entity-encoder type-bias and env-layer gradients in one pass");
   m.def("replay_gather", &replay_gather, "minibatch gather from an HBM replay pool into time-major rows (one launch)");
+  m.def("replay_sample", &replay_sample, "prioritised mixture sampler over the replay ring (two launches, no sync)");
+  m.def("seq_priority", &seq_priority, "per-sequence priorities (P, non-finite flag) from a step's advantages");
+  m.def("priority_scatter", &priority_scatter, "priority[idx] = P of the step's sequences + non-finite counter");
   m.def("vtrace_step", &vtrace_step, "V-trace advantages / value targets of a minibatch from the step's own values",
         py::arg("z"), py::arg("vcol"), py::arg("lp"), py::arg("mu"), py::arg("vt"), py::arg("B"), py::arg("S"),
         py::arg("gamma"), py::arg("lam"), py::arg("rho_bar") = 1.0, py::arg("c_bar") = 1.0);

@@ -127,4 +127,15 @@ hipError_t dca_enc_small_grads(const float* z, int ldz, const float* dtl, int U,
 hipError_t dca_replay_gather(const void* const* src, void* const* dst, const long long* row_bytes, const int* per_step,
                              int nf, const long long* idx, int S, int B, hipStream_t st);
 
+// replay_sample.hip: prioritised mixture sampler (block sums + one-workgroup draw kernel), per-sequence priorities of a
+// learner step (out (2, B): P, non-finite flag) and their scatter into the ring's priority vector
+hipError_t dca_replay_sample(const float* pri, const long long* version, double* bsum, float* bmax, int capacity,
+                             int size, int cursor, int m, float recent_frac, long long cur_version,
+                             unsigned long long seed, long long* ctr, long long* idx_out, int B, float* pmax_out,
+                             double* stats, float* u_out, hipStream_t st);
+hipError_t dca_seq_priority(const float* adv, const float* vt, float* out, int B, int S, float eta, float alpha,
+                            float eps, hipStream_t st);
+hipError_t dca_priority_scatter(float* pri, int capacity, const long long* idx, const float* pf, int B,
+                                float* nonfinite, hipStream_t st);
+
 }  // extern "C"

@@ -40,6 +40,14 @@ def main(argv=None):
     ap.add_argument('--replay-gb', type=float, default=0.0, help='on-HBM replay the learner samples from')
     ap.add_argument('--replay-recent', type=int, default=0,
                     help='sample the replay\'s newest N sequences only (0 = the whole buffer)')
+    ap.add_argument('--replay-sampler', default='uniform', choices=['uniform', 'mixture'],
+                    help='mixture: newest-window draws + prioritised draws over the whole replay')
+    ap.add_argument('--replay-recent-frac', type=float, default=0.5,
+                    help='mixture sampler: share of the draws from the --replay-recent newest sequences')
+    ap.add_argument('--replay-priority-alpha', type=float, default=0.6)
+    ap.add_argument('--replay-priority-eta', type=float, default=0.9)
+    ap.add_argument('--replay-ratio', type=float, default=1.0,
+                    help='replay steps per iteration as a multiple (>= 1) of the fresh minibatch count')
     ap.add_argument('--device', default='cuda')
     ap.add_argument('--snapshot-lags', default='120,300,600',
                     help='seconds of training: every row also plays the weights from that long ago (comma list, '
@@ -74,6 +82,9 @@ def main(argv=None):
                            snapshot_lags=tuple(float(x) for x in a.snapshot_lags.split(',') if x.strip()),
                            snapshot_games=a.snapshot_games, old_logp=a.old_logp, advantages=a.advantages,
                            weight_lag=a.weight_lag, replay_recent=a.replay_recent,
+                           replay_sampler=a.replay_sampler, replay_recent_frac=a.replay_recent_frac,
+                           replay_priority_alpha=a.replay_priority_alpha,
+                           replay_priority_eta=a.replay_priority_eta, replay_ratio=a.replay_ratio,
                            league_matrix_n=a.league_matrix)
 
 
