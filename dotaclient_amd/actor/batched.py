@@ -73,16 +73,70 @@ def frag_weight(w: torch.Tensor, mode: int) -> torch.Tensor:
     return src.reshape(N // 16, 16, K // kg, 4, e).permute(0, 2, 3, 1, 4).contiguous().view(-1)
 
 
+def plan_tiles(n: int, n_sets: int, even: bool = True) -> int:
+    """16-row tiles that hold any assignment of ``n`` slots to ``n_sets`` weight sets (each set's run is padded to a
+    multiple of 16); ``even``: rounded up to an even count (the bf16 encoder's workgroup owns two tiles)."""
+    T = (n + 15 * n_sets) // 16
+    return T + (T & 1) if even else T
+
+
+def build_set_plan(h_set, n_sets: int, rows_out: np.ndarray, tile_set_out: np.ndarray) -> int:
+    """The launch plan of a step whose slots run on different weight sets (the kernels' ``MIX`` variants).
+
+    ``h_set`` (n,) int: weight set of every slot. Writes ``rows_out`` (16·T,) int32 — every slot exactly once,
+    grouped by set, ascending within a set, each set's run padded to a multiple of 16 with -1 — and ``tile_set_out``
+    (T,) int32, the set of each 16-row tile (-1: unused trailing tile). ``T >= plan_tiles(n, n_sets, even=False)``
+    always suffices. Raises ``ValueError`` for a set index outside ``[0, n_sets)``: the kernels never see an
+    unvalidated index. Returns the number of tiles used."""
+    h = np.asarray(h_set)
+    if h.ndim != 1 or h.size < 1 or not np.issubdtype(h.dtype, np.integer):
+        raise ValueError('build_set_plan: h_set must be a non-empty (n,) integer array')
+    if n_sets < 1 or int(h.min()) < 0 or int(h.max()) >= n_sets:
+        raise ValueError(f'build_set_plan: set indices must lie in [0, {n_sets})')
+    T = int(tile_set_out.shape[0])
+    counts = np.bincount(h, minlength=n_sets)
+    used = int(((counts + 15) // 16).sum())
+    if rows_out.shape != (16 * T,) or used > T:
+        raise ValueError(f'build_set_plan: rows_out must be (16·T,) with T >= {used} tiles')
+    order = np.argsort(h, kind='stable')
+    rows_out[:] = -1
+    tile_set_out[:] = -1
+    src = tile = 0
+    for s in range(n_sets):
+        c = int(counts[s])
+        if c == 0:
+            continue
+        nt = (c + 15) // 16
+        rows_out[16 * tile:16 * tile + c] = order[src:src + c]
+        tile_set_out[tile:tile + nt] = s
+        src += c
+        tile += nt
+    return tile
+
+
 class GpuActorPolicy:
     """Fixed-slot batched policy step on one GPU: LSTM / linear-RNN policies, 1v1 or 5v5 (entity attention), bf16
-    operands on hand-written MFMA kernels (``CORE_MODE`` 1; :class:`F32ActorPolicy` is the IEEE-fp32 twin)."""
+    operands on hand-written MFMA kernels (``CORE_MODE`` 1; :class:`F32ActorPolicy` is the IEEE-fp32 twin).
+
+    ``n_sets > 1`` (1v1 policies): the policy holds ``n_sets`` weight versions (``load_weights(state, set=k)``) and
+    every slot steps on the version ``h_set[slot]`` names — still one encoder, one core and one sampler launch: the
+    kernels' 16-row tiles are gathered from slots that share a set (:func:`build_set_plan`, rebuilt when ``h_set``
+    changed). A slot changes its set together with a reset of its state."""
 
     CORE_MODE = 1        # ops/csrc/actor_core.hip: 0 = IEEE fp32 (f32 MFMA), 1 = bf16 operands
 
     def __init__(self, policy: Policy, n_slots: int, device='cuda', seed: int = 0, use_graph: bool = True,
-                 record: bool = True, inputs_from: Optional['GpuActorPolicy'] = None, raw: bool = False):
+                 record: bool = True, inputs_from: Optional['GpuActorPolicy'] = None, raw: bool = False,
+                 n_sets: int = 1):
         from .. import ops
         self.C = ops.require()
+        self.n_sets = int(n_sets)
+        if self.n_sets < 1:
+            raise ValueError('n_sets must be >= 1')
+        if self.n_sets > 1 and policy.config.entity_attention:
+            raise ValueError('n_sets > 1: the entity-attention (5v5) step runs one weight version per launch')
+        if self.n_sets > 1 and inputs_from is not None:
+            raise ValueError('n_sets > 1: a mixed step stages its own observations (no inputs_from)')
         # raw: observations staged as compact raw unit records (features/raw.py, 32 B per unit slot + a 16 B hero
         # record per slot instead of 40 B of features + an 8 B handle) and featurized by the step's first kernel
         # (ops/csrc/featurize.hip); the host's native engine then skips the per-unit feature arithmetic
@@ -121,6 +175,17 @@ class GpuActorPolicy:
         self.h_keep, self.h_active = self.in_pack.host['keep'], self.in_pack.host['active']
         self.h_keep.fill_(1.0)
         self.h_active.fill_(1.0)
+        self._in_last = 'active'                       # last region of the step's one H2D copy
+        self._plan_kw = {}
+        if self.n_sets > 1:
+            # per-slot weight set (staged by the caller) and the launch plan built from it: the plan's two regions
+            # follow keep / active in the pack, so they cross in the same copy
+            self.h_set = torch.zeros(self.n, dtype=torch.int32, pin_memory=True)
+            self.h_plan_rows, self.h_tile_set = self.in_pack.host['rows'], self.in_pack.host['tile_set']
+            self._in_last = 'tile_set'
+            self._plan_kw = {'rows': self.in_pack.dev['rows'], 'tile_set': self.in_pack.dev['tile_set']}
+            self._planned = None
+            self._plan()
         self.d_env = self.in_pack.dev['env']
         self.d_keep = self.in_pack.dev['keep']
         self.d_active = self.in_pack.dev['active']     # 0 → slot not stepped: LSTM state left untouched
@@ -130,7 +195,7 @@ class GpuActorPolicy:
         n, U, dev = self.n, self.U, self.device
         self.in_pack = _Pack([('env', (n, 3), torch.float32), ('hero', (n, 4), torch.float32),
                               ('raw', (n, U, self.RAW_WORDS), torch.int32), ('keep', (n, 1), torch.float32),
-                              ('active', (n,), torch.float32)], dev)
+                              ('active', (n,), torch.float32)] + self._plan_fields(), dev)
         if inputs_from is not None:
             if (inputs_from.n, inputs_from.U) != (n, U) or not inputs_from.raw:
                 raise ValueError('inputs_from: slot count / layout / staging mismatch')
@@ -150,7 +215,8 @@ class GpuActorPolicy:
         # ONE packed pinned staging buffer and ONE device mirror per direction: a step's inputs cross PCIe in one copy
         # and its outputs come back in one (each separate copy was a DMA dispatch of its own inside the graph)
         self.in_pack = _Pack([('env', (n, 3), torch.float32), ('units', (n, U, 10), ud), ('handles', (n, U), hd),
-                              ('keep', (n, 1), torch.float32), ('active', (n,), torch.float32)], dev)
+                              ('keep', (n, 1), torch.float32), ('active', (n,), torch.float32)]
+                             + self._plan_fields(), dev)
         if inputs_from is not None:
             # a second policy over the same observations (league opponents): share the staged inputs; keep/active
             # stay per policy (its own pack's env / units / handles regions are unused)
@@ -164,6 +230,19 @@ class GpuActorPolicy:
         # the kernels read the staged dtypes as they are (fp8 step: fp16 features, int32 handles)
         self.d_units = self.in_pack.dev['units']
         self.d_handles = self.in_pack.dev['handles']
+
+    def _plan_fields(self):
+        if self.n_sets == 1:
+            return []
+        T = plan_tiles(self.n, self.n_sets)
+        return [('rows', (16 * T,), torch.int32), ('tile_set', (T,), torch.int32)]
+
+    def _plan(self):
+        """Rebuild the launch plan in the staging pack if ``h_set`` changed since the last step."""
+        h = self.h_set.numpy()
+        if self._planned is None or not np.array_equal(h, self._planned):
+            build_set_plan(h, self.n_sets, self.h_plan_rows.numpy(), self.h_tile_set.numpy())
+            self._planned = h.copy()
 
     def _alloc_state(self):
         n, A, dev = self.n, self.A, self.device
@@ -194,13 +273,22 @@ class GpuActorPolicy:
         self.stream = torch.cuda.Stream(device=dev)
 
     @torch.no_grad()
-    def load_weights(self, policy_or_state):
+    def load_weights(self, policy_or_state, set: int = 0):
         """(Re)load weights in place — buffers keep their addresses, so a captured graph stays valid. The copies
-        run on the step stream, so they are ordered after the previous replay and before the next one."""
+        run on the step stream, so they are ordered after the previous replay and before the next one. ``set``: the
+        weight set written (``n_sets > 1``)."""
+        self._check_set(set)
         if hasattr(self, 'stream'):
             with torch.cuda.stream(self.stream):
-                return self._load_weights(policy_or_state)
-        return self._load_weights(policy_or_state)
+                return self._load_weights(policy_or_state, set)
+        return self._load_weights(policy_or_state, set)
+
+    def _check_set(self, set: int):
+        if not 0 <= int(set) < self.n_sets:
+            raise ValueError(f'weight set {set} outside [0, {self.n_sets})')
+
+    def _dst(self, k: str, set: int) -> torch.Tensor:
+        return self.w[k][set] if self.n_sets > 1 else self.w[k]
 
     @torch.no_grad()
     def weight_dict(self, policy_or_state):
@@ -216,9 +304,10 @@ class GpuActorPolicy:
 
     @torch.no_grad()
     def load_weight_dict(self, w: Dict[str, torch.Tensor], ready: Optional[torch.cuda.Event] = None,
-                         producer: Optional[torch.cuda.Stream] = None):
+                         producer: Optional[torch.cuda.Stream] = None, set: int = 0):
         """Copy a :meth:`weight_dict` operand set (built on ``producer``, complete at ``ready``) into this policy's
-        buffers, ordered on its step stream."""
+        buffers (``n_sets > 1``: into weight set ``set``), ordered on its step stream."""
+        self._check_set(set)
         other = producer is not None and producer != self.stream
         with torch.cuda.stream(self.stream):
             if ready is not None:
@@ -227,17 +316,22 @@ class GpuActorPolicy:
                 if isinstance(v, torch.Tensor):
                     if other:
                         v.record_stream(self.stream)   # the producer's allocator must not reuse it before this copy
-                    self.w[k].copy_(v)
+                    self._dst(k, set).copy_(v)
 
-    def _load_weights(self, policy_or_state):
+    def _load_weights(self, policy_or_state, set: int = 0):
         sd = policy_or_state.state_dict() if isinstance(policy_or_state, torch.nn.Module) else policy_or_state
         w = self._weight_dict(sd)
         if not hasattr(self, 'w'):
+            if self.n_sets > 1:
+                # every operand stacked over the sets (the kernels offset by set × per-set size); all sets start
+                # from the weights given at construction
+                w = {k: (torch.stack([v] * self.n_sets).contiguous() if isinstance(v, torch.Tensor) else v)
+                     for k, v in w.items()}
             self.w = w
         else:
             for k, v in w.items():
                 if isinstance(v, torch.Tensor):
-                    self.w[k].copy_(v)
+                    self._dst(k, set).copy_(v)
 
     def _weight_dict(self, sd) -> Dict[str, torch.Tensor]:
         dev, mode, cfg = self.device, self.CORE_MODE, self.cfg
@@ -299,7 +393,7 @@ class GpuActorPolicy:
             C.featurize_raw(self.d_raw, self.d_hero, self.d_units, self.d_handles)
         x896, emb, arg = C.encoder_fwd(self.d_units, self.d_env, w['w1'], w['b1'], w['wt'], w['bt'], w['we'],
                                        w['be'], list(cfg.layout.counts), bool(cfg.compat_bugs),
-                                       exact=self.CORE_MODE == 0)
+                                       exact=self.CORE_MODE == 0, **self._plan_kw)
         if cfg.entity_attention:
             # 5v5 pre-LN self-attention over the 64 unit slots + pools of the attended embeddings, ONE kernel
             # (ops/csrc/attn_block.hip, the learner's forward); E1 is the pointer head's unit embedding
@@ -311,7 +405,7 @@ class GpuActorPolicy:
             x896[:, 768:896] = x896[:, 512:640]
         C.actor_core(x896, w['cpre'], w['bpre'], w['cg'], w['bg'], w['ch'], w['bh'], self.h, self.c,
                      self.d_keep.view(-1), self.z, self.CORE_MODE, cfg.rnn != 'lstm', active=self.d_active,
-                     bump=self.ctr)
+                     bump=self.ctr, **self._plan_kw)
         C.sample_actions(self.z, emb, self.d_handles, self.seed, self.ctr, self.idx, self.act, self.msk, self.logp,
                          self.value)
 
@@ -328,7 +422,7 @@ class GpuActorPolicy:
                 ip['handles'].copy_(self.h_handles, non_blocking=True)
             self.in_pack.copy_range('keep', 'active')
         else:
-            self.in_pack.copy_range('env', 'active')          # one H2D copy of the whole staged step
+            self.in_pack.copy_range('env', self._in_last)     # one H2D copy of the whole staged step
 
     def _d2h(self):
         self.out_pack.copy_range('idx', 'msk' if self.record else 'value', to_host=True)
@@ -385,6 +479,8 @@ class GpuActorPolicy:
         ``out['hidden']`` (k, 2, H) — the trajectory's stored states (codec ``hiddens``)."""
         if self.use_graph and self.graph is None:
             self.capture()
+        if self.n_sets > 1:
+            self._plan()
         with torch.cuda.stream(self.stream):
             self._snap_n = 0
             if snapshot_rows is not None and len(snapshot_rows) and self.cfg.rnn == 'lstm':
@@ -548,11 +644,11 @@ class Fp8ActorPolicy(GpuActorPolicy):
         if self.raw:
             C.featurize_raw(self.d_raw, self.d_hero, self.d_units, self.d_handles)
         x896, emb = C.encoder_fp8(self.d_units, self.d_env, w['w1'], w['b1'], w['wt8'], w['st8'], w['bt'], w['we'],
-                                  w['be'], list(cfg.layout.counts))
+                                  w['be'], list(cfg.layout.counts), **self._plan_kw)
         if cfg.compat_bugs:
             x896[:, 768:896] = x896[:, 512:640]
         C.actor_fp8(x896, w['wpre8'], w['spre'], w['bpre32'], w['wg8'], w['sg'], w['bg'], w['wh8'], w['sh8'],
-                    w['bh'], self.h, self.c, self.d_keep.view(-1), self.z, self.d_active, self.ctr)
+                    w['bh'], self.h, self.c, self.d_keep.view(-1), self.z, self.d_active, self.ctr, **self._plan_kw)
         C.sample_actions(self.z, emb, self.d_handles, self.seed, self.ctr, self.idx, self.act, self.msk, self.logp,
                          self.value)
 
@@ -560,19 +656,31 @@ class Fp8ActorPolicy(GpuActorPolicy):
 class TorchSlotPolicy:
     """:class:`GpuActorPolicy`'s host interface (staged ``h_*`` inputs, per-slot LSTM state, ``keep``/``active``,
     :meth:`step_async`/:meth:`wait`, hidden snapshots) over the eager torch policy on any device — the CPU actor
-    (BASELINE config 1: no GPU) and policies the fused graph does not cover (5v5 entity attention)."""
+    (BASELINE config 1: no GPU) and policies the fused graph does not cover (5v5 entity attention).
+    ``n_sets > 1``: one eager policy per weight set (``load_weights(state, set=k)``), each stepping the active slots
+    whose ``h_set`` names it — the mixed step's host interface without a GPU."""
 
     def __init__(self, policy: Policy, n_slots: int, device='cpu', seed: int = 0, record: bool = True,
-                 inputs_from: Optional['TorchSlotPolicy'] = None, **_):
+                 inputs_from: Optional['TorchSlotPolicy'] = None, n_sets: int = 1, **_):
         from .runner import PolicyRunner
         self.cfg = policy.config
         self.n = n_slots
         self.U = self.cfg.layout.max_units
         self.A = 21 + self.U
         self.device = torch.device(device)
-        self.policy = type(policy)(self.cfg).to(self.device).eval()
-        self.load_weights(policy)
-        self.runner = PolicyRunner(self.policy, device=self.device, seed=seed)
+        self.n_sets = int(n_sets)
+        if self.n_sets < 1:
+            raise ValueError('n_sets must be >= 1')
+        if self.n_sets > 1 and inputs_from is not None:
+            raise ValueError('n_sets > 1: a mixed step stages its own observations (no inputs_from)')
+        self.policies = [type(policy)(self.cfg).to(self.device).eval() for _ in range(self.n_sets)]
+        self.policy = self.policies[0]
+        for k in range(self.n_sets):
+            self.load_weights(policy, set=k)
+        self.runners = [PolicyRunner(p, device=self.device, seed=seed + 15485863 * k)
+                        for k, p in enumerate(self.policies)]
+        self.runner = self.runners[0]
+        self.h_set = torch.zeros(n_slots, dtype=torch.int32)
         n, U = n_slots, self.U
         if inputs_from is not None:
             if (inputs_from.n, inputs_from.U) != (n, U):
@@ -591,9 +699,11 @@ class TorchSlotPolicy:
         self._out = None
 
     @torch.no_grad()
-    def load_weights(self, policy_or_state):
+    def load_weights(self, policy_or_state, set: int = 0):
+        if not 0 <= int(set) < self.n_sets:
+            raise ValueError(f'weight set {set} outside [0, {self.n_sets})')
         sd = policy_or_state.state_dict() if isinstance(policy_or_state, torch.nn.Module) else policy_or_state
-        self.policy.load_state_dict({k: v.detach().to(self.device) for k, v in sd.items()}, strict=True)
+        self.policies[set].load_state_dict({k: v.detach().to(self.device) for k, v in sd.items()}, strict=True)
 
     def step_async(self, snapshot_rows: Optional[np.ndarray] = None):
         keep = self.h_keep.numpy()
@@ -603,14 +713,19 @@ class TorchSlotPolicy:
         if snapshot_rows is not None and len(snapshot_rows) and self.recurrent:
             rows = np.asarray(snapshot_rows)
             out['hidden'] = np.stack([self.h[rows], self.c[rows]], 1)
-        act = np.flatnonzero(self.h_active.numpy() > 0)
         n, A = self.n, self.A
         out.update(idx=np.zeros((n, 4), np.int32), logp=np.zeros(n, np.float32), value=np.zeros(n, np.float32),
                    actions=np.zeros((n, A), np.uint8), masks=np.zeros((n, A), np.uint8))
-        if len(act):
+        hset = self.h_set.numpy()
+        if self.n_sets > 1 and (hset.min() < 0 or hset.max() >= self.n_sets):
+            raise ValueError(f'h_set: set indices must lie in [0, {self.n_sets})')
+        for k, runner in enumerate(self.runners):
+            on = self.h_active.numpy() > 0
+            act = np.flatnonzero(on & (hset == k) if self.n_sets > 1 else on)
+            if not len(act):
+                continue
             hid = (self.h[act], self.c[act]) if self.recurrent else None
-            o, nh = self.runner.step(self.h_env.numpy()[act], self.h_units.numpy()[act], self.h_handles.numpy()[act],
-                                     hid)
+            o, nh = runner.step(self.h_env.numpy()[act], self.h_units.numpy()[act], self.h_handles.numpy()[act], hid)
             out['idx'][act] = np.stack([o.enum, o.x, o.y, o.target], 1)
             out['logp'][act], out['value'][act] = o.logp, o.value
             out['actions'][act], out['masks'][act] = o.actions, o.masks

@@ -76,13 +76,14 @@ def evaluate_vs_default_bot(policy, n_games: int = 128, device='cuda', seed: int
 
 def evaluate_vs_snapshot(policy, snapshot_state, n_games: int = 64, device='cuda', seed: int = 777,
                          max_dota_time: float = 600.0, threads: int = 8, timeout: float = 900.0,
-                         precision: str = 'fp32') -> Dict[str, float]:
+                         precision: str = 'fp32', league_step: str = 'separate') -> Dict[str, float]:
     """Head-to-head games of ``policy`` (the current weights) against a frozen past snapshot of the same network
     (``snapshot_state``: a state_dict) — the discriminating signal once the default-bot win rate saturates, and one
     entry of the league's win-rate matrix. Every game is a league game of the self-play engine (VecActor with
     ``latest_weights_prob`` 0: one team — Radiant or Dire at random — plays the snapshot, the other the current
     weights; reference mini-league, agent.py:760-765); a fixed ``seed`` replays the same openings. Returns
-    ``win_rate`` (wins + ½ time-limit draws, per game), ``wins`` / ``losses`` / ``draws`` and ``games``."""
+    ``win_rate`` (wins + ½ time-limit draws, per game), ``wins`` / ``losses`` / ``draws`` and ``games``.
+    ``league_step='mixed'``: both versions in ONE policy step per group (VecActor ``league_step``) instead of two."""
     from .league import League
     from .vec import VecActor
     from .weights import WeightStore
@@ -94,7 +95,8 @@ def evaluate_vs_snapshot(policy, snapshot_state, n_games: int = 64, device='cuda
     mode = '5v5' if policy.config.layout.counts[0] > 1 else '1v1'
     va = VecActor(ws, n_games, None, device=device, mode=mode, seed=seed, rollout_size=10 ** 9,
                   max_dota_time=max_dota_time, threads=threads, groups=1, stagger=False, league=lg,
-                  latest_weights_prob=0.0, opponent_refresh=10 ** 9, tag=f'snap{seed}', precision=precision)
+                  latest_weights_prob=0.0, opponent_refresh=10 ** 9, tag=f'snap{seed}', precision=precision,
+                  league_step=league_step)
     t0 = time.time()
     try:
         while lg.games.get(0, 0.0) < n_games:
@@ -115,7 +117,7 @@ def evaluate_vs_snapshot(policy, snapshot_state, n_games: int = 64, device='cuda
 
 
 def league_matrix(snapshots, config, n_games: int = 32, device='cuda', seed: int = 991, max_dota_time: float = 600.0,
-                  threads: int = 8, precision: str = 'fp32') -> Dict[str, object]:
+                  threads: int = 8, precision: str = 'fp32', league_step: str = 'separate') -> Dict[str, object]:
     """Pairwise win rates of league snapshots ``[(label, state_dict), …]`` (oldest first): entry [i][j] is the
     score of snapshot i against snapshot j over ``n_games`` games (wins + ½ draws; [j][i] = 1 − [i][j]). A healthy
     league is (mostly) increasing along each row's diagonal direction: later snapshots beat earlier ones."""
@@ -128,7 +130,8 @@ def league_matrix(snapshots, config, n_games: int = 32, device='cuda', seed: int
         pol.load_state_dict(snapshots[i][1])
         for j in range(i):
             r = evaluate_vs_snapshot(pol, snapshots[j][1], n_games=n_games, device=device, seed=seed + 31 * i + j,
-                                     max_dota_time=max_dota_time, threads=threads, precision=precision)
+                                     max_dota_time=max_dota_time, threads=threads, precision=precision,
+                                     league_step=league_step)
             m[i][j] = r['win_rate']
             m[j][i] = 1.0 - r['win_rate']
     return {'labels': labels, 'win_rate': m, 'games_per_pair': n_games}

@@ -19,6 +19,11 @@ keeps its opponent snapshot for its whole length: each group holds up to two opp
 staged observations, their own LSTM state) — new opponent games join the *current* one; every
 ``opponent_refresh`` finished opponent games a fresh snapshot is sampled into the *other* one once its games have
 drained, and it becomes current. Results are fed back to the league per game.
+
+``league_step='mixed'``: instead of extra policies, each group's ONE policy holds three weight sets (0: the latest
+weights, 1-2: the two rotating opponent snapshots) and every slot steps on its game's set in the same launch
+(:class:`~dotaclient_amd.actor.batched.GpuActorPolicy` ``n_sets``): one policy step per group step whatever the
+league does, no second or third pass over all slots and no output splice.
 """
 from __future__ import annotations
 
@@ -37,9 +42,13 @@ logger = logging.getLogger(__name__)
 MODES = {'1v1': 0, '5v5': 1, 'vs_default_bot': 2, 'vs_default_bot_5v5': 3}
 
 
+LEAGUE_STEPS = ('separate', 'mixed')
+
+
 class _Opponent:
-    def __init__(self, gp):
-        self.gp = gp
+    def __init__(self, gp=None, set: Optional[int] = None):
+        self.gp = gp            # 'separate': this snapshot's own slot policy
+        self.set = set          # 'mixed': its weight set in the group's policy
         self.version: Optional[int] = None
         self.games = 0          # games in flight bound to this policy
 
@@ -98,7 +107,8 @@ class VecActor:
                  latest_weights_prob: float = 1.0, hidden_stride: int = 256, threads: int = 8, groups: int = 2,
                  league=None, opponent_refresh: int = 64, start_time: float = -10.0,
                  fog: bool = True, tag: str = 'vec', stagger: bool = False, wire: bool = False,
-                 precision: str = 'bf16', ring_sink=None, raw: Optional[bool] = None):
+                 precision: str = 'bf16', ring_sink=None, raw: Optional[bool] = None,
+                 league_step: str = 'separate'):
         from .. import native
         if not native.AVAILABLE:
             raise RuntimeError('VecActor needs the native module (python -m dotaclient_amd.native.build)')
@@ -143,6 +153,13 @@ class VecActor:
         if raw and not fused:
             raise ValueError('raw observation staging needs a fused GPU actor policy')
         self.raw = fused if raw is None else bool(raw)
+        # league opponents: their own slot policies ('separate') or weight sets 1-2 of the group's one policy ('mixed')
+        if league_step not in LEAGUE_STEPS:
+            raise ValueError(f'league_step must be one of {LEAGUE_STEPS}, got {league_step!r}')
+        if league_step == 'mixed' and fused and self.cfg.entity_attention:
+            raise ValueError("league_step='mixed': the fused entity-attention (5v5) step runs one weight version "
+                             "per launch")
+        self.league_step = league_step
         groups = max(1, min(int(groups), n_games))
         sizes = [n_games // groups + (1 if i < n_games % groups else 0) for i in range(groups)]
         self.groups = [_Group(self, i, sizes[i], seed * 7919 + i) for i in range(groups)]
@@ -193,6 +210,8 @@ class VecActor:
             kw['compact'] = False          # (feature staging: the native VecEnv writes the fp32 buffers in place)
         if self.raw:
             kw['raw'] = True
+        if self.league_step == 'mixed':
+            kw['n_sets'] = 3               # 0: latest weights, 1-2: the two rotating opponent snapshots
         return kw
 
     def _sample_opponent(self):
@@ -201,15 +220,20 @@ class VecActor:
         return self.store.oldest_weights()
 
     def _opponent(self, g: _Group, k: int) -> _Opponent:
+        while len(g.opp) <= k and self.league_step == 'mixed':
+            g.opp.append(_Opponent(set=1 + len(g.opp)))
         while len(g.opp) <= k:
             gp = make_slot_policy(self.policy, g.S, device=self.device, seed=g.seed + 104729 * (len(g.opp) + 1),
                                   inputs_from=g.gp, **self._policy_kw())
             g.opp.append(_Opponent(gp))
         return g.opp[k]
 
-    def _load_opponent(self, o: _Opponent):
+    def _load_opponent(self, g: _Group, o: _Opponent):
         vs = self._sample_opponent()
-        o.gp.load_weights(vs[1])
+        if o.gp is None:
+            g.gp.load_weights(vs[1], set=o.set)
+        else:
+            o.gp.load_weights(vs[1])
         o.version = int(vs[0])
 
     def _assign_opponents(self, g: _Group, reset: np.ndarray):
@@ -223,13 +247,13 @@ class VecActor:
         if len(new_games) == 0:
             return
         if not g.opp:
-            self._load_opponent(self._opponent(g, 0))
+            self._load_opponent(g, self._opponent(g, 0))
             g.cur_opp = 0
             g.refresh_mark = self.opp_games_finished
         elif self.opp_games_finished - g.refresh_mark >= self.opponent_refresh:
             other = self._opponent(g, 1 - g.cur_opp)
             if other.games == 0:      # rotate once the other policy's games have drained
-                self._load_opponent(other)
+                self._load_opponent(g, other)
                 g.cur_opp = 1 - g.cur_opp
                 g.refresh_mark = self.opp_games_finished
         g.game_opp[new_games] = g.cur_opp
@@ -264,7 +288,17 @@ class VecActor:
         act = g.active.astype(np.float32)
         g.opp_rows = {}
         busy = [k for k, o in enumerate(g.opp) if o.games > 0]
-        if busy:
+        if self.league_step == 'mixed':
+            # one step for everyone: opponent slots run on their game's snapshot set, the rest on the latest weights
+            hset = g.gp.h_set.numpy()
+            hset[:] = 0
+            opp_slots = np.asarray(g.ve.opponent_slots(), dtype=np.int64)
+            if len(opp_slots):
+                hset[opp_slots] = 1 + g.game_opp[opp_slots // g.ppg]
+                opp_mask = np.zeros(g.S, bool)
+                opp_mask[opp_slots] = True
+                need = need[~opp_mask[need]]
+        elif busy:
             slot_opp = np.repeat(g.game_opp, g.ppg)
             opp_mask = np.zeros(g.S, bool)
             opp_mask[g.ve.opponent_slots()] = True

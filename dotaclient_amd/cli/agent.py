@@ -58,6 +58,9 @@ def build_parser():
     ap.add_argument('--actor-precision', type=str, default='bf16', choices=['bf16', 'fp32', 'fp8'],
                     help='vec runtime policy step: bf16, fp32 (IEEE fp32, the reference actor\'s precision; 1v1) or '
                          'fp8 (e4m3 MFMA kernel; 1v1 LSTM-512 policies)')
+    ap.add_argument('--league-step', type=str, default='separate', choices=['separate', 'mixed'],
+                    help='vec runtime league opponents: separate = an extra policy step per busy opponent snapshot; '
+                         'mixed = one step per group, every slot on its own weight version (1v1 policies)')
     ap.add_argument('--league', type=str, default='oldest', choices=['oldest', 'uniform', 'recent', 'pfsp'],
                     help='opponent sampling over the weight history when not playing the latest weights')
     return ap
@@ -159,7 +162,7 @@ def _run_vec(args, ws, broker, league, device, seed, cfg):
                   mode='5v5' if cfg.layout.counts[0] > 1 else '1v1', seed=seed, rollout_size=args.rollout_size,
                   max_dota_time=args.max_dota_time, latest_weights_prob=args.use_latest_weights_prob,
                   hidden_stride=args.hidden_stride, threads=args.threads, league=league, stagger=True,
-                  precision=args.actor_precision)
+                  precision=args.actor_precision, league_step=args.league_step)
     try:
         va.run(n_games=args.n_games)
     except Exception:

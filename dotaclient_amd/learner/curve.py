@@ -39,7 +39,7 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
                        advantages: str = 'vtrace-step', weight_lag: int = 0,
                        replay_recent: int = 0, replay_sampler: str = 'uniform', replay_recent_frac: float = 0.5,
                        replay_priority_alpha: float = 0.6, replay_priority_eta: float = 0.9,
-                       replay_ratio: float = 1.0) -> List[Dict]:
+                       replay_ratio: float = 1.0, league_step: str = 'separate') -> List[Dict]:
     """Train for ``budget`` seconds (evaluations excluded) and return the evaluation rows (the first one before
     any training). ``on_row`` is called with every row as it is produced; ``save_model``: path that receives the
     final weights (a reference-format state_dict file). ``eval_precision``: the validation games' policy step.
@@ -55,7 +55,8 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
     whole buffer, or over its ``replay_recent`` newest sequences; ``replay_sampler='mixture'`` draws a share
     ``replay_recent_frac`` from those newest and the rest by priority over the whole ring (``replay_priority_alpha`` /
     ``replay_priority_eta``, ops/replay.py), ``replay_ratio`` > 1 runs that many times more replay steps per
-    iteration."""
+    iteration. ``league_step='mixed'``: league opponents (the actors' and the snapshot evaluations') are stepped in
+    the same launch as the latest weights (VecActor ``league_step``)."""
     import json
     import os
 
@@ -110,7 +111,7 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
     va = VecActor(ws, games, broker.publish_experience, device=device, seed=seed, rollout_size=9999,
                   max_dota_time=max_dota_time, hidden_stride=seq_len, threads=threads, stagger=True, mode=mode,
                   league=lg, latest_weights_prob=latest_weights_prob if lg is not None else 1.0,
-                  precision=actor_precision)
+                  precision=actor_precision, league_step=league_step)
     stop, pause, paused, err = threading.Event(), threading.Event(), threading.Event(), []
     rows: List[Dict] = []
     sync = torch.cuda.synchronize if str(device).startswith('cuda') else (lambda: None)
@@ -146,7 +147,7 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
                 continue
             r = evaluate_vs_snapshot(opt.policy, past[-1][1], n_games=snapshot_games, device=device,
                                      seed=eval_seed + int(lag), max_dota_time=max_dota_time, threads=threads,
-                                     precision=eval_precision)
+                                     precision=eval_precision, league_step=league_step)
             tag = f'{int(lag) // 60}min' if lag >= 60 else f'{int(lag)}s'
             row[f'snap/win_rate_vs_{tag}'] = r['win_rate']
             row[f'snap/age_s_vs_{tag}'] = round(t_now - past[-1][0], 1)
@@ -211,7 +212,7 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
             pick = [snaps[round(i * (len(snaps) - 1) / (k - 1))] for i in range(k)]
             lm = league_matrix([(f't{int(t)}s', sd) for t, sd in pick], opt.policy.config,
                                n_games=snapshot_games, device=device, max_dota_time=max_dota_time, threads=threads,
-                               precision=eval_precision)
+                               precision=eval_precision, league_step=league_step)
             row = {'league_matrix': lm, 't_train': round(trained, 1)}
             rows.append(row)
             if on_row is not None:

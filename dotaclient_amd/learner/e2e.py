@@ -195,7 +195,7 @@ def open_node_broker(addr: str, drop_oldest: bool = True):
 def _actor_process_main(addr: str, model: str, games: int, threads: int, seq_len: int, rollout_size: int,
                         max_dota_time: float, device: str, seed: int, stop, ready, steps, failed, tag: str = 'a0',
                         league: Optional[str] = None, latest_weights_prob: float = 1.0,
-                        precision: str = 'bf16'):
+                        precision: str = 'bf16', league_step: str = 'separate'):
     """Actor role of :func:`measure_e2e_node`: a process of its own (own interpreter and GIL) that plays ``games``
     VecActor games on its GPU, pushes whole-game rollouts into the node's experience queue and hot-swaps every model
     the learner's rank 0 publishes (reference agent.py:855-902 with the model subscription of 198-223). It tears its
@@ -236,7 +236,8 @@ def _actor_process_main(addr: str, model: str, games: int, threads: int, seq_len
         va = VecActor(ws, games, br.publish_experience, device=device, mode=mode, seed=seed,
                       rollout_size=rollout_size, max_dota_time=max_dota_time, hidden_stride=seq_len, threads=threads,
                       stagger=True, tag=f'{tag}.vec', league=lg, latest_weights_prob=latest_weights_prob,
-                      precision=precision, ring_sink=sink, groups=groups)   # (game ids unique across the node)
+                      precision=precision, ring_sink=sink, groups=groups,   # (game ids unique across the node)
+                      league_step=league_step)
         for _ in range(3):
             va.step()
         ready.set()
@@ -319,7 +320,7 @@ def measure_e2e_node(model: str = 'lstm512', device='cuda', duration: float = 20
                      old_logp: str = 'actor', advantages: str = 'vtrace-step', replay_recent: int = 0,
                      replay_sampler: str = 'uniform', replay_recent_frac: float = 0.5,
                      replay_priority_alpha: float = 0.6, replay_priority_eta: float = 0.9,
-                     replay_ratio: float = 1.0) -> Dict[str, float]:
+                     replay_ratio: float = 1.0, league_step: str = 'separate') -> Dict[str, float]:
     """The reference's node topology end to end (optimizer.py:144-150, 274-287; ks-app/components/optimizer.jsonnet:
     79-174): ONE experience queue per node fed by actor processes, ``WORLD_SIZE`` learner ranks (one per GPU, DDP
     over RCCL) consuming disjoint rollouts from it as competing consumers, and rank 0 alone checkpointing and
@@ -341,6 +342,7 @@ def measure_e2e_node(model: str = 'lstm512', device='cuda', duration: float = 20
     (learner/replay.py) instead of the iteration's fresh rollouts only — sampled uniformly (over the ring or its
     ``replay_recent`` newest), or with ``replay_sampler='mixture'`` a share ``replay_recent_frac`` from those newest
     and the rest by priority (ops/replay.py); ``replay_ratio`` > 1 multiplies the replay steps per iteration.
+    ``league_step='mixed'``: the actors step league opponents in the same launch as the latest weights (VecActor).
 
     ``actor_procs`` > 1 splits each rank's ``games`` and ``threads`` over that many actor processes (each with its own
     interpreter, GIL and graphs on the rank's GPU): the actor loop's Python between its native parallel regions is
@@ -435,7 +437,7 @@ def measure_e2e_node(model: str = 'lstm512', device='cuda', duration: float = 20
                                    args=(addr, model, g_k, t_k, seq_len, rollout_size, max_dota_time, str(device),
                                          11 + 7919 * rank + 104729 * k, stop, readies[k], counters[k], failed,
                                          f'a{rank}' if K == 1 else f'a{rank}_{k}', league, latest_weights_prob,
-                                         actor_precision))
+                                         actor_precision, league_step))
                 proc.start()
                 procs.append(proc)
         finally:
@@ -565,7 +567,7 @@ def measure_e2e_node(model: str = 'lstm512', device='cuda', duration: float = 20
                          actor=(f'one process per rank over the node {transport} broker' if K == 1 else
                                 f'{K} processes per rank over the node {transport} broker'), learners=world,
                          league=league, latest_weights_prob=latest_weights_prob, actor_precision=actor_precision,
-                         replay_gb=replay_gb,
+                         league_step=league_step, replay_gb=replay_gb,
                          # what was allocated (≤ replay_gb: the learner keeps the replay within the free HBM)
                          replay_gb_allocated=(opt.replay.nbytes / 1e9 if opt is not None and opt.replay is not None
                                               else 0.),

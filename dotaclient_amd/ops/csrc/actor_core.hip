@@ -133,10 +133,15 @@ struct CoreArgs {
   float* z;                              // (n, 160) fp32
   int n;
   long long* bump;                       // the sampler's step counter, += 1 here (null: the caller bumps it)
+  // MIX (slots on different weight sets in one launch, actor/batched.py build_set_plan): row p of the launch is slot
+  // rows[p] (-1: pad), tile t (rows 16t … 16t+15) runs on weight set tile_set[t] (-1: unused tile); the weight and
+  // bias arguments then hold n_sets sets back to back
+  const int* rows; const int* tile_set; int n_sets;
 };
 
-// MODE 0 fp32 / 1 bf16 operands; XF32: x896 arrives fp32 (else bf16); H hidden width; LIN: linear recurrent layer
-template <int MODE, bool XF32, int H, bool LIN>
+// MODE 0 fp32 / 1 bf16 operands; XF32: x896 arrives fp32 (else bf16); H hidden width; LIN: linear recurrent layer;
+// MIX: per-tile weight set and slot gather (see CoreArgs) — the arithmetic of a row is the same either way
+template <int MODE, bool XF32, int H, bool LIN, bool MIX>
 __global__ __launch_bounds__(NT, 2) void actor_core_kernel(CoreArgs A) {
   using M = Mma<MODE>;
   using AT = typename M::T;
@@ -159,6 +164,7 @@ __global__ __launch_bounds__(NT, 2) void actor_core_kernel(CoreArgs A) {
   static_assert(BM * LHB * ES <= SX, "the bf16 heads image must fit the x image");
   __shared__ __attribute__((aligned(16))) char lds[BYTES];
   __shared__ float s_keep[BM], s_act[BM];
+  __shared__ int s_slot[BM];                     // MIX: the tile's slot ids (-1: pad row)
   char* ximg = lds + OX;
   char* gimg = lds + OG;
   float* cs = reinterpret_cast<float*>(lds + OC);
@@ -169,8 +175,24 @@ __global__ __launch_bounds__(NT, 2) void actor_core_kernel(CoreArgs A) {
   const int q = lane >> 4, cl = lane & 15;
   const int row0 = blockIdx.x * BM, n = A.n;
   const int r = tid / TPR, sub = tid % TPR;      // staging: TPR threads per row
-  const int grow_r = min(row0 + r, n - 1);
-  const bool row_ok = row0 + r < n;
+  int grow_r;
+  bool row_ok;
+  if constexpr (MIX) {
+    // (uniform for the workgroup, before the first barrier) an unused tile, or a set index the plan cannot hold
+    const int set = A.tile_set[blockIdx.x];
+    if (set < 0 || set >= A.n_sets) return;
+    A.wpre += (size_t)set * (PD * XD * ES / 16); A.bpre += set * PD;
+    A.wg += (size_t)set * (GN * GK * ES / 16); A.bg += set * GN;
+    A.wh += (size_t)set * (ZD * H * ES / 16); A.bh += set * ZD;
+    const int slot = A.rows[row0 + r];
+    row_ok = slot >= 0 && slot < n;
+    // pad rows load a valid slot of this tile (its first row is never a pad) and store nothing
+    grow_r = row_ok ? slot : min(max(A.rows[row0], 0), n - 1);
+    if (sub == 0) s_slot[r] = row_ok ? slot : -1;
+  } else {
+    grow_r = min(row0 + r, n - 1);
+    row_ok = row0 + r < n;
+  }
 
   // ---- stage 0: biases; keep / active; the x896 rows → A image
   for (int i = tid; i < NB; i += NT) {
@@ -317,8 +339,13 @@ __global__ __launch_bounds__(NT, 2) void actor_core_kernel(CoreArgs A) {
           const float b = col_b[PD + GN + col];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const int grow = row0 + 4 * q + e;
-            if (grow < n) A.z[(size_t)grow * ZD + col] = acc[i][e] + b;
+            if constexpr (MIX) {
+              const int grow = s_slot[4 * q + e];
+              if (grow >= 0) A.z[(size_t)grow * ZD + col] = acc[i][e] + b;
+            } else {
+              const int grow = row0 + 4 * q + e;
+              if (grow < n) A.z[(size_t)grow * ZD + col] = acc[i][e] + b;
+            }
           }
         }
       });
@@ -331,18 +358,23 @@ __global__ __launch_bounds__(NT, 2) void actor_core_kernel(CoreArgs A) {
 extern "C" hipError_t dca_actor_core(const void* x896, int x_f32, const void* wpre, const float* bpre, const void* wg,
                                      const float* bg, const void* wh, const float* bh, float* h, float* c,
                                      const float* keep, const float* active, float* z, int n, int hidden, int linear,
-                                     int mode, long long* bump, hipStream_t st) {
+                                     int mode, long long* bump, hipStream_t st, const int* rows,
+                                     const int* tile_set, int n_tiles, int n_sets) {
   if (n < 1 || mode < 0 || mode > 1) return hipErrorInvalidValue;
+  const bool mix = rows != nullptr;
+  if (mix && (tile_set == nullptr || n_tiles < 1 || n_sets < 1)) return hipErrorInvalidValue;
   CoreArgs a{x896, static_cast<const uint4*>(wpre), bpre, static_cast<const uint4*>(wg), bg,
-             static_cast<const uint4*>(wh), bh, h, c, keep, active, z, n, bump};
-  const dim3 grid((n + BM - 1) / BM), block(NT);
-#define DCA_CORE(MD, XF, HH, LN) hipLaunchKernelGGL((actor_core_kernel<MD, XF, HH, LN>), grid, block, 0, st, a)
+             static_cast<const uint4*>(wh), bh, h, c, keep, active, z, n, bump, rows, tile_set, n_sets};
+  const dim3 grid(mix ? n_tiles : (n + BM - 1) / BM), block(NT);
+#define DCA_CORE(MD, XF, HH, LN)                                                            \
+  if (mix) hipLaunchKernelGGL((actor_core_kernel<MD, XF, HH, LN, true>), grid, block, 0, st, a); \
+  else hipLaunchKernelGGL((actor_core_kernel<MD, XF, HH, LN, false>), grid, block, 0, st, a)
 #define DCA_CORE_H(MD, XF)                                                   \
   if (linear) {                                                              \
     if (hidden != 256) return hipErrorInvalidValue;                          \
     DCA_CORE(MD, XF, 256, true);                                             \
-  } else if (hidden == 512) DCA_CORE(MD, XF, 512, false);                    \
-  else if (hidden == 128) DCA_CORE(MD, XF, 128, false);                      \
+  } else if (hidden == 512) { DCA_CORE(MD, XF, 512, false); }                \
+  else if (hidden == 128) { DCA_CORE(MD, XF, 128, false); }                  \
   else return hipErrorInvalidValue;
   if (mode == 0) {
     if (!x_f32) return hipErrorInvalidValue;       // the fp32 step takes the exact encoder's fp32 features

@@ -126,8 +126,14 @@ struct Fp8Args {
   float* z;                              // (n, 160) fp32
   int n;
   long long* bump;                       // the sampler's step counter, += 1 here (null: the caller bumps it)
+  // MIX (slots on different weight sets in one launch, actor/batched.py build_set_plan): row p of the launch is slot
+  // rows[p] (-1: pad), tile t (rows 16t … 16t+15) runs on weight set tile_set[t] (-1: unused tile); the weight, scale
+  // and bias arguments then hold n_sets sets back to back
+  const int* rows; const int* tile_set; int n_sets;
 };
 
+// MIX: per-tile weight set and slot gather (see Fp8Args) — the arithmetic of a row is the same either way
+template <bool MIX>
 __global__ __launch_bounds__(NT) void actor_fp8_kernel(Fp8Args A) {
   __shared__ __attribute__((aligned(16))) unsigned char a8x[BM * LDX];   // x896 fp8, later h fp8 (heads)
   __shared__ __attribute__((aligned(16))) unsigned char a8g[BM * LDG];   // [pre | h] fp8
@@ -145,8 +151,25 @@ __global__ __launch_bounds__(NT) void actor_fp8_kernel(Fp8Args A) {
   const int row0 = blockIdx.x * BM;
   const int n = A.n;
   const int r = tid / TPR, sub = tid % TPR;            // staging: TPR threads per row
-  const int grow_r = min(row0 + r, n - 1);
-  const bool row_ok = row0 + r < n;
+  __shared__ int s_slot[BM];                           // MIX: the tile's slot ids (-1: pad row)
+  int grow_r;
+  bool row_ok;
+  if constexpr (MIX) {
+    // (uniform for the workgroup, before the first barrier) an unused tile, or a set index the plan cannot hold
+    const int set = A.tile_set[blockIdx.x];
+    if (set < 0 || set >= A.n_sets) return;
+    A.wpre += (size_t)set * (PD * XD / 32); A.spre += set * PD; A.bpre += set * PD;
+    A.wg += (size_t)set * (GD * KG / 32); A.sg += set * GD; A.bg += set * GD;
+    A.wh += (size_t)set * (ZD * HD / 32); A.sh += set * ZD; A.bh += set * ZD;
+    const int slot = A.rows[row0 + r];
+    row_ok = slot >= 0 && slot < n;
+    // pad rows load a valid slot of this tile (its first row is never a pad) and store nothing
+    grow_r = row_ok ? slot : min(max(A.rows[row0], 0), n - 1);
+    if (sub == 0) s_slot[r] = row_ok ? slot : -1;
+  } else {
+    grow_r = min(row0 + r, n - 1);
+    row_ok = row0 + r < n;
+  }
 
   // ---- stage 0: x896 row → fp8 (per-row scale); keep / active flags; column scales / biases
   for (int i = tid; i < PD + GD + ZD; i += NT) {
@@ -348,8 +371,14 @@ __global__ __launch_bounds__(NT) void actor_fp8_kernel(Fp8Args A) {
           const float sc = col_s[PD + GD + col], b = col_b[PD + GD + col];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const int row = 4 * q + e, grow = row0 + row;
-            if (grow < n) A.z[(size_t)grow * ZD + col] = acc[i][e] * s_row[2][row] * sc + b;
+            const int row = 4 * q + e;
+            if constexpr (MIX) {
+              const int grow = s_slot[row];
+              if (grow >= 0) A.z[(size_t)grow * ZD + col] = acc[i][e] * s_row[2][row] * sc + b;
+            } else {
+              const int grow = row0 + row;
+              if (grow < n) A.z[(size_t)grow * ZD + col] = acc[i][e] * s_row[2][row] * sc + b;
+            }
           }
         }
       });
@@ -594,6 +623,9 @@ struct EncW8Args {
   int N, U;
   int nrun[8];                           // same-type runs of wave w's unit segment (≤ 3)
   int rt[8][3], rb[8][3], re[8][3];      // run k: type, first unit, one past the last unit
+  // MIX (see Fp8Args): row p of the launch is slot rows[p] (-1: pad), 16-row tile t runs on weight set tile_set[t]
+  // (-1: unused tile); the weight, scale and bias arguments hold n_sets sets back to back
+  const int* rows; const int* tile_set; int n_sets;
 };
 constexpr int EWT = 512, EWP = 136;      // threads; bf16 pitch of a wave's 16 × 128 emb tile
 
@@ -602,7 +634,14 @@ __device__ __forceinline__ int ord_key(float f) {     // float order as signed-i
   return b < 0 ? b ^ 0x7fffffff : b;
 }
 
-template <bool F16>
+// MIX kernels: weight set `set` of an argument that holds the sets back to back (else the argument as it is)
+template <bool MIX, class T>
+__device__ __forceinline__ const T* set_ptr(const T* p, int set, int per_set) {
+  if constexpr (MIX) return p + (size_t)set * per_set;
+  else return p;
+}
+
+template <bool F16, bool MIX>
 __global__ __launch_bounds__(EWT, 1) void encoder_fp8w_kernel(EncW8Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned us[];          // the 16 rows' unit features, raw bytes
   __shared__ __attribute__((aligned(16))) float w1s[11 * 128];            // W1ᵀ (feature-major), then b1
@@ -612,8 +651,33 @@ __global__ __launch_bounds__(EWT, 1) void encoder_fp8w_kernel(EncW8Args a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r0 = blockIdx.x * EBR, N = a.N, U = a.U;
-  const int nrows = min(EBR, N - r0);
-  {   // unit features → LDS by LDS-DMA (rows past N read the last valid dword; their outputs are never stored)
+  __shared__ int s_slot[EBR];                                             // MIX: the tile's slot ids (-1: pad row)
+  int set = 0;
+  if constexpr (MIX) {
+    // (uniform for the workgroup, before the first barrier) an unused tile, or a set index the plan cannot hold
+    set = a.tile_set[blockIdx.x];
+    if (set < 0 || set >= a.n_sets) return;
+    if (tid < EBR) {
+      const int slot = a.rows[r0 + tid];
+      s_slot[tid] = slot >= 0 && slot < N ? slot : -1;
+    }
+    // unit features → LDS by LDS-DMA, each row from its slot (pad rows read the tile's first slot, never a pad;
+    // their outputs are never stored)
+    typedef __attribute__((address_space(1))) void gvoid;
+    typedef __attribute__((address_space(3))) void lvoid;
+    constexpr int ES = F16 ? 2 : 4;
+    const int rdw = U * 10 * ES / 4, total = EBR * rdw;
+    const unsigned* src = static_cast<const unsigned*>(a.units);
+    const int first = min(max(a.rows[r0], 0), N - 1);
+    for (int q0 = 64 * w; q0 < total; q0 += EWT) {
+      const int d = min(q0 + lane, total - 1), row = d / rdw;
+      const int slot = a.rows[r0 + row];
+      const int srow = slot >= 0 && slot < N ? slot : first;
+      __builtin_amdgcn_global_load_lds((gvoid*)(src + (size_t)srow * rdw + (d - row * rdw)), (lvoid*)(us + q0), 4,
+                                       0, 0);
+    }
+  } else {   // unit features → LDS by LDS-DMA (rows past N read the last valid dword; their outputs are never stored)
+    const int nrows = min(EBR, N - r0);
     typedef __attribute__((address_space(1))) void gvoid;
     typedef __attribute__((address_space(3))) void lvoid;
     constexpr int ES = F16 ? 2 : 4;
@@ -625,22 +689,28 @@ __global__ __launch_bounds__(EWT, 1) void encoder_fp8w_kernel(EncW8Args a) {
   }
   for (int i = tid; i < 11 * 128; i += EWT) {
     const int f = i >> 7, c = i & 127;
-    w1s[i] = f < 10 ? a.w1[c * 10 + f] : a.b1[c];
+    w1s[i] = f < 10 ? set_ptr<MIX>(a.w1, set, 1280)[c * 10 + f] : set_ptr<MIX>(a.b1, set, 128)[c];
   }
   for (int i = tid; i < 6 * 128; i += EWT) {
-    cscale[i] = a.st[i];
-    cbias[i] = a.bt[i];
+    cscale[i] = set_ptr<MIX>(a.st, set, 768)[i];
+    cbias[i] = set_ptr<MIX>(a.bt, set, 768)[i];
   }
   for (int i = tid; i < 6 * EBR * 128; i += EWT) pool[i] = (int)0x80000000;
   {   // env embedding: row tid>>5, columns 4(tid&31) … +3
-    const int row = r0 + (tid >> 5), c0 = 4 * (tid & 31);
+    int row = r0 + (tid >> 5);
+    const int c0 = 4 * (tid & 31);
+    if constexpr (MIX) {
+      row = a.rows[row];
+      if (row < 0) row = N;                       // pad row: nothing stored
+    }
     if (row < N) {
       const float e0 = a.env[row * 3], e1 = a.env[row * 3 + 1], e2 = a.env[row * 3 + 2];
+      const float *we = set_ptr<MIX>(a.we, set, 384), *be = set_ptr<MIX>(a.be, set, 128);
       short o[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int c = c0 + j;
-        o[j] = dca::f2bf(fmaxf(a.be[c] + a.we[c * 3] * e0 + a.we[c * 3 + 1] * e1 + a.we[c * 3 + 2] * e2, 0.f));
+        o[j] = dca::f2bf(fmaxf(be[c] + we[c * 3] * e0 + we[c * 3 + 1] * e1 + we[c * 3 + 2] * e2, 0.f));
       }
       *reinterpret_cast<uint2*>(a.x896 + (size_t)row * 896 + c0) =
           make_uint2((unsigned)(unsigned short)o[0] | ((unsigned)(unsigned short)o[1] << 16),
@@ -650,8 +720,9 @@ __global__ __launch_bounds__(EWT, 1) void encoder_fp8w_kernel(EncW8Args a) {
   const int nr = a.nrun[w];
   i32x8 WA[8], WB[8];
   auto load = [&](i32x8 (&W)[8], int tau) {
+    const i32x8* wt = set_ptr<MIX>(a.wt, set, 6 * 128 * 128 / 32);
 #pragma unroll
-    for (int t = 0; t < 8; ++t) W[t] = a.wt[((size_t)tau * 8 + t) * 64 + lane];
+    for (int t = 0; t < 8; ++t) W[t] = wt[((size_t)tau * 8 + t) * 64 + lane];
   };
   if (nr > 0) load(WA, a.rt[w][0]);
   if (nr > 1) load(WB, a.rt[w][1]);
@@ -730,7 +801,12 @@ __global__ __launch_bounds__(EWT, 1) void encoder_fp8w_kernel(EncW8Args a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = 4 * i + kc;
-      if (r0 + row < N)
+      if constexpr (MIX) {
+        const int slot = s_slot[row];
+        if (slot >= 0)
+          *reinterpret_cast<uint4*>(a.emb + ((size_t)slot * U + u) * 128 + 8 * m) =
+              *reinterpret_cast<const uint4*>(tile + row * EWP + 8 * m);
+      } else if (r0 + row < N)
         *reinterpret_cast<uint4*>(a.emb + ((size_t)(r0 + row) * U + u) * 128 + 8 * m) =
             *reinterpret_cast<const uint4*>(tile + row * EWP + 8 * m);
     }
@@ -749,7 +825,11 @@ __global__ __launch_bounds__(EWT, 1) void encoder_fp8w_kernel(EncW8Args a) {
   // pools → x896[:, 128 + 128τ + c], 8 columns (16 B) per store
   for (int i = tid; i < 6 * EBR * 16; i += EWT) {
     const int tau = i / (EBR * 16), rem = i - tau * EBR * 16, row = rem >> 4, ch = rem & 15;
-    if (r0 + row >= N) continue;
+    int grow = r0 + row;
+    if constexpr (MIX) {
+      grow = s_slot[row];
+      if (grow < 0) continue;
+    } else if (grow >= N) continue;
     const int* pk = pool + (tau * EBR + row) * 128 + 8 * ch;
     unsigned o[4];
 #pragma unroll
@@ -758,7 +838,7 @@ __global__ __launch_bounds__(EWT, 1) void encoder_fp8w_kernel(EncW8Args a) {
       const float hi = __int_as_float(ord_key(__int_as_float(pk[2 * j + 1])));
       o[j] = (unsigned)(unsigned short)dca::f2bf(lo) | ((unsigned)(unsigned short)dca::f2bf(hi) << 16);
     }
-    *reinterpret_cast<uint4*>(a.x896 + (size_t)(r0 + row) * 896 + 128 + 128 * tau + 8 * ch) =
+    *reinterpret_cast<uint4*>(a.x896 + (size_t)grow * 896 + 128 + 128 * tau + 8 * ch) =
         make_uint4(o[0], o[1], o[2], o[3]);
   }
 }
@@ -771,11 +851,17 @@ __global__ __launch_bounds__(EWT, 1) void encoder_fp8w_kernel(EncW8Args a) {
 extern "C" hipError_t dca_actor_fp8(const short* x896, const void* wpre, const float* spre, const float* bpre,
                                     const void* wg, const float* sg, const float* bg, const void* wh, const float* sh,
                                     const float* bh, float* h, float* c, const float* keep, const float* active,
-                                    float* z, int n, long long* bump, hipStream_t stream) {
+                                    float* z, int n, long long* bump, hipStream_t stream, const int* rows,
+                                    const int* tile_set, int n_tiles, int n_sets) {
   if (n < 1) return hipSuccess;
   Fp8Args a{x896, reinterpret_cast<const i32x8*>(wpre), spre, bpre, reinterpret_cast<const i32x8*>(wg), sg, bg,
-            reinterpret_cast<const i32x8*>(wh), sh, bh, h, c, keep, active, z, n, bump};
-  hipLaunchKernelGGL(actor_fp8_kernel, dim3((n + BM - 1) / BM), dim3(NT), 0, stream, a);
+            reinterpret_cast<const i32x8*>(wh), sh, bh, h, c, keep, active, z, n, bump, rows, tile_set, n_sets};
+  if (rows != nullptr) {   // mixed weight sets: one workgroup per planned tile
+    if (tile_set == nullptr || n_tiles < 1 || n_sets < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(actor_fp8_kernel<true>, dim3(n_tiles), dim3(NT), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL(actor_fp8_kernel<false>, dim3((n + BM - 1) / BM), dim3(NT), 0, stream, a);
+  }
   return hipGetLastError();
 }
 
@@ -785,11 +871,16 @@ extern "C" hipError_t dca_actor_fp8(const short* x896, const void* wpre, const f
 extern "C" hipError_t dca_encoder_fp8(const void* units, int f16, const float* env, const float* w1, const float* b1,
                                       const void* wt, const float* st, const float* bt, const float* we,
                                       const float* be, short* x896, short* emb, int N, int U, const int* counts,
-                                      int per_unit, hipStream_t stream) {
+                                      int per_unit, hipStream_t stream, const int* rows, const int* tile_set,
+                                      int n_tiles, int n_sets) {
   if (N < 1) return hipSuccess;
   if (U < 1 || U > EMAXU) return hipErrorInvalidValue;
+  const bool mix = rows != nullptr;
+  // mixed weight sets: the wave-parallel form only (one workgroup per planned tile); no per-unit fallback
+  if (mix && (per_unit || tile_set == nullptr || n_tiles < 1 || n_sets < 1)) return hipErrorInvalidValue;
   if (!per_unit) {   // wave-parallel form: U units in type order as 8 contiguous segments of ≤ 3 same-type runs
-    EncW8Args b{units, env, w1, b1, reinterpret_cast<const i32x8*>(wt), st, bt, we, be, x896, emb, N, U, {}, {}, {}, {}};
+    EncW8Args b{units, env, w1, b1, reinterpret_cast<const i32x8*>(wt), st, bt, we, be, x896, emb, N, U, {}, {}, {}, {},
+                rows, tile_set, n_sets};
     int tof[EMAXU], acc = 0;
     bool ok = true;
     for (int t = 0; t < 6; ++t) {
@@ -812,11 +903,15 @@ extern "C" hipError_t dca_encoder_fp8(const void* units, int f16, const float* e
     }
     if (ok) {
       const size_t lds = ((size_t)EBR * U * 10 * (f16 ? 2 : 4) + 15) / 16 * 16;
-      const dim3 grid((N + EBR - 1) / EBR);
-      if (f16) hipLaunchKernelGGL(encoder_fp8w_kernel<true>, grid, dim3(EWT), lds, stream, b);
-      else hipLaunchKernelGGL(encoder_fp8w_kernel<false>, grid, dim3(EWT), lds, stream, b);
+      const dim3 grid(mix ? n_tiles : (N + EBR - 1) / EBR);
+      if (mix) {
+        if (f16) hipLaunchKernelGGL((encoder_fp8w_kernel<true, true>), grid, dim3(EWT), lds, stream, b);
+        else hipLaunchKernelGGL((encoder_fp8w_kernel<false, true>), grid, dim3(EWT), lds, stream, b);
+      } else if (f16) hipLaunchKernelGGL((encoder_fp8w_kernel<true, false>), grid, dim3(EWT), lds, stream, b);
+      else hipLaunchKernelGGL((encoder_fp8w_kernel<false, false>), grid, dim3(EWT), lds, stream, b);
       return hipGetLastError();
     }
+    if (mix) return hipErrorInvalidValue;       // this layout needs the per-unit form: not covered
   }
   EncFp8Args a{units, env, w1, b1, reinterpret_cast<const i32x8*>(wt), st, bt, we, be, x896, emb, N, U, {}};
   int acc = 0;

@@ -306,6 +306,31 @@ std::vector<torch::Tensor> heads_loss(torch::Tensor z, torch::Tensor emb, torch:
   return {dz, dtl, part, logp};
 }
 
+// Optional set plan of a mixed-weight-set actor launch (actor/batched.py build_set_plan, which validates the set
+// indices): rows (16·T) int32 slot of each launch row (-1: pad), tile_set (T) int32 weight set of each 16-row tile
+// (-1: unused). Given together or not at all.
+struct SetPlan {
+  const int* rows = nullptr;
+  const int* tile_set = nullptr;
+  int n_tiles = 0;
+  explicit operator bool() const { return rows != nullptr; }
+};
+static SetPlan set_plan(const c10::optional<torch::Tensor>& rows, const c10::optional<torch::Tensor>& tile_set,
+                        const char* who) {
+  const bool r = rows && rows->defined(), t = tile_set && tile_set->defined();
+  TORCH_CHECK(r == t, who, ": rows and tile_set come together");
+  SetPlan p;
+  if (!r) return p;
+  CHECK_DEV(*rows); CHECK_CONTIG(*rows); CHECK_DT(*rows, at::kInt);
+  CHECK_DEV(*tile_set); CHECK_CONTIG(*tile_set); CHECK_DT(*tile_set, at::kInt);
+  TORCH_CHECK(tile_set->numel() >= 1 && rows->numel() == 16 * tile_set->numel(), who,
+              ": rows (16·T) int32, tile_set (T) int32");
+  p.rows = ptr<int>(*rows);
+  p.tile_set = ptr<int>(*tile_set);
+  p.n_tiles = (int)tile_set->numel();
+  return p;
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // Fused entity encoder. units (N,U,10) f32, env (N,3) f32, w1 (128,10), b1 (128), wt (6,128,128) bf16 or f32,
 // bt (6,128), we (128,3), be (128); counts = 6 unit counts. Returns (x896 (N,896), emb (N,U,128), argmax u8
@@ -314,7 +339,8 @@ std::vector<torch::Tensor> encoder_fwd(torch::Tensor units, torch::Tensor env, t
                                        torch::Tensor wt, torch::Tensor bt, torch::Tensor we, torch::Tensor be,
                                        std::vector<int64_t> counts, bool compat, bool exact,
                                        c10::optional<torch::Tensor> x896_out, c10::optional<torch::Tensor> emb_out,
-                                       c10::optional<torch::Tensor> arg_out) {
+                                       c10::optional<torch::Tensor> arg_out, c10::optional<torch::Tensor> rows,
+                                       c10::optional<torch::Tensor> tile_set) {
   CHECK_F32(units); CHECK_F32(env); CHECK_F32(w1); CHECK_F32(b1); CHECK_DEV(wt); CHECK_CONTIG(wt); CHECK_F32(bt);
   CHECK_F32(we); CHECK_F32(be);
   const bool f32w = wt.scalar_type() == at::kFloat;
@@ -323,8 +349,19 @@ std::vector<torch::Tensor> encoder_fwd(torch::Tensor units, torch::Tensor env, t
   TORCH_CHECK(units.dim() == 3 && units.size(2) == 10, "units must be (N,U,10)");
   const int N = units.size(0), U = units.size(1);
   TORCH_CHECK(env.size(0) == N && env.size(1) == 3, "env must be (N,3)");
-  TORCH_CHECK(w1.size(0) == 128 && w1.size(1) == 10 && wt.size(0) == 6 && wt.size(1) == 128 && wt.size(2) == 128,
-              "weight shapes");
+  const SetPlan plan = set_plan(rows, tile_set, "encoder_fwd");
+  int64_t S = 1;
+  if (plan) {   // mixed weight sets (the actor step): every weight argument carries a leading n_sets dimension
+    S = b1.numel() / 128;
+    TORCH_CHECK(S >= 1 && w1.numel() == S * 128 * 10 && b1.numel() == S * 128 && wt.numel() == S * 6 * 128 * 128 &&
+                bt.numel() == S * 6 * 128 && we.numel() == S * 128 * 3 && be.numel() == S * 128,
+                "encoder_fwd: weights of a mixed step are (n_sets, …)");
+    TORCH_CHECK(exact || !f32w, "encoder_fwd: a mixed step runs the bf16 or the exact fp32 encoder");
+    TORCH_CHECK(exact || plan.n_tiles % 2 == 0, "encoder_fwd: the bf16 encoder takes an even tile count");
+  } else {
+    TORCH_CHECK(w1.size(0) == 128 && w1.size(1) == 10 && wt.size(0) == 6 && wt.size(1) == 128 && wt.size(2) == 128,
+                "weight shapes");
+  }
   TORCH_CHECK(counts.size() == 6, "counts must have 6 entries");
   int c[6];
   int64_t tot = 0;
@@ -337,7 +374,8 @@ std::vector<torch::Tensor> encoder_fwd(torch::Tensor units, torch::Tensor env, t
   auto arg = out_or_new(arg_out, {N, 6, 128}, o.dtype(at::kByte), "arg_out");
   hip_check(dca_encoder_fwd(ptr<float>(units), ptr<float>(env), ptr<float>(w1), ptr<float>(b1), wt.data_ptr(),
                             ptr<float>(bt), ptr<float>(we), ptr<float>(be), x896.data_ptr(), emb.data_ptr(),
-                            ptr<unsigned char>(arg), N, U, c, compat ? 1 : 0, cur_stream(), exact ? 2 : (f32w ? 1 : 0)),
+                            ptr<unsigned char>(arg), N, U, c, compat ? 1 : 0, cur_stream(), exact ? 2 : (f32w ? 1 : 0),
+                            plan.rows, plan.tile_set, plan.n_tiles, (int)S),
             "dca_encoder_fwd");
   return {x896, emb, arg};
 }
@@ -450,15 +488,23 @@ void lstm_cell(torch::Tensor gates, torch::Tensor h, torch::Tensor c, torch::Ten
 void actor_fp8(torch::Tensor x896, torch::Tensor wpre, torch::Tensor spre, torch::Tensor bpre, torch::Tensor wg,
                torch::Tensor sg, torch::Tensor bg, torch::Tensor wh, torch::Tensor sh, torch::Tensor bh,
                torch::Tensor h, torch::Tensor c, torch::Tensor keep, torch::Tensor z,
-               c10::optional<torch::Tensor> active, c10::optional<torch::Tensor> bump) {
+               c10::optional<torch::Tensor> active, c10::optional<torch::Tensor> bump,
+               c10::optional<torch::Tensor> rows, c10::optional<torch::Tensor> tile_set) {
   CHECK_BF16(x896); CHECK_U8(wpre); CHECK_U8(wg); CHECK_U8(wh);
   CHECK_F32(spre); CHECK_F32(bpre); CHECK_F32(sg); CHECK_F32(bg); CHECK_F32(sh); CHECK_F32(bh);
   CHECK_F32(h); CHECK_F32(c); CHECK_F32(keep); CHECK_F32(z);
   const int n = x896.size(0);
+  const SetPlan plan = set_plan(rows, tile_set, "actor_fp8");
+  // mixed weight sets: every weight argument carries a leading n_sets dimension
+  const int64_t S = plan ? bpre.numel() / 256 : 1;
+  TORCH_CHECK(S >= 1, "actor_fp8: weight sets");
   TORCH_CHECK(x896.dim() == 2 && x896.size(1) == 896, "actor_fp8: x896 (n, 896)");
-  TORCH_CHECK(wpre.numel() == 256 * 896 && spre.numel() == 256 && bpre.numel() == 256, "actor_fp8: pre-RNN 256x896");
-  TORCH_CHECK(wg.numel() == 2048 * 768 && sg.numel() == 2048 && bg.numel() == 2048, "actor_fp8: gates 2048x768");
-  TORCH_CHECK(wh.numel() == 160 * 512 && sh.numel() == 160 && bh.numel() == 160, "actor_fp8: heads 160x512");
+  TORCH_CHECK(wpre.numel() == S * 256 * 896 && spre.numel() == S * 256 && bpre.numel() == S * 256,
+              "actor_fp8: pre-RNN 256x896");
+  TORCH_CHECK(wg.numel() == S * 2048 * 768 && sg.numel() == S * 2048 && bg.numel() == S * 2048,
+              "actor_fp8: gates 2048x768");
+  TORCH_CHECK(wh.numel() == S * 160 * 512 && sh.numel() == S * 160 && bh.numel() == S * 160,
+              "actor_fp8: heads 160x512");
   TORCH_CHECK(h.dim() == 2 && h.size(0) == n && h.size(1) == 512 && c.sizes() == h.sizes() && keep.numel() == n,
               "actor_fp8: h, c (n, 512), keep (n)");
   TORCH_CHECK(z.dim() == 2 && z.size(0) == n && z.size(1) == 160, "actor_fp8: z (n, 160)");
@@ -470,7 +516,8 @@ void actor_fp8(torch::Tensor x896, torch::Tensor wpre, torch::Tensor spre, torch
   }
   hip_check(dca_actor_fp8(ptr<short>(x896), wpre.data_ptr(), ptr<float>(spre), ptr<float>(bpre), wg.data_ptr(),
                           ptr<float>(sg), ptr<float>(bg), wh.data_ptr(), ptr<float>(sh), ptr<float>(bh), ptr<float>(h),
-                          ptr<float>(c), ptr<float>(keep), act, ptr<float>(z), n, bump_ptr(bump), cur_stream()),
+                          ptr<float>(c), ptr<float>(keep), act, ptr<float>(z), n, bump_ptr(bump), cur_stream(),
+                          plan.rows, plan.tile_set, plan.n_tiles, (int)S),
             "dca_actor_fp8");
 }
 
@@ -480,7 +527,8 @@ void actor_fp8(torch::Tensor x896, torch::Tensor wpre, torch::Tensor spre, torch
 void actor_core(torch::Tensor x896, torch::Tensor wpre, torch::Tensor bpre, torch::Tensor wg, torch::Tensor bg,
                 torch::Tensor wh, torch::Tensor bh, torch::Tensor h, torch::Tensor c, torch::Tensor keep,
                 torch::Tensor z, int64_t mode, bool linear, c10::optional<torch::Tensor> active,
-                c10::optional<torch::Tensor> bump) {
+                c10::optional<torch::Tensor> bump, c10::optional<torch::Tensor> rows,
+                c10::optional<torch::Tensor> tile_set) {
   CHECK_DEV(x896); CHECK_CONTIG(x896); CHECK_DEV(wpre); CHECK_CONTIG(wpre); CHECK_DEV(wg); CHECK_CONTIG(wg);
   CHECK_DEV(wh); CHECK_CONTIG(wh); CHECK_F32(bpre); CHECK_F32(bg); CHECK_F32(bh); CHECK_F32(h); CHECK_F32(c);
   CHECK_F32(keep); CHECK_F32(z);
@@ -494,9 +542,13 @@ void actor_core(torch::Tensor x896, torch::Tensor wpre, torch::Tensor bpre, torc
   TORCH_CHECK(x896.dim() == 2 && x896.size(1) == 896, "actor_core: x896 (n, 896)");
   TORCH_CHECK(linear ? H == 256 : (H == 512 || H == 128), "actor_core: hidden 512 / 128 (LSTM) or 256 (linear)");
   const int64_t gn = linear ? H : 4 * H, gk = linear ? 256 : 256 + H;
-  TORCH_CHECK(wpre.numel() == 256 * 896 && bpre.numel() == 256, "actor_core: pre-RNN 256x896");
-  TORCH_CHECK(wg.numel() == gn * gk && bg.numel() == gn, "actor_core: recurrent weights");
-  TORCH_CHECK(wh.numel() == 160 * H && bh.numel() == 160, "actor_core: heads 160 x hidden");
+  const SetPlan plan = set_plan(rows, tile_set, "actor_core");
+  // mixed weight sets: every weight argument carries a leading n_sets dimension
+  const int64_t S = plan ? bpre.numel() / 256 : 1;
+  TORCH_CHECK(S >= 1, "actor_core: weight sets");
+  TORCH_CHECK(wpre.numel() == S * 256 * 896 && bpre.numel() == S * 256, "actor_core: pre-RNN 256x896");
+  TORCH_CHECK(wg.numel() == S * gn * gk && bg.numel() == S * gn, "actor_core: recurrent weights");
+  TORCH_CHECK(wh.numel() == S * 160 * H && bh.numel() == S * 160, "actor_core: heads 160 x hidden");
   TORCH_CHECK(h.dim() == 2 && h.size(0) == n && c.sizes() == h.sizes() && keep.numel() == n,
               "actor_core: h, c (n, hidden), keep (n)");
   TORCH_CHECK(z.dim() == 2 && z.size(0) == n && z.size(1) == 160, "actor_core: z (n, 160)");
@@ -509,7 +561,7 @@ void actor_core(torch::Tensor x896, torch::Tensor wpre, torch::Tensor bpre, torc
   hip_check(dca_actor_core(x896.data_ptr(), x32 ? 1 : 0, wpre.data_ptr(), ptr<float>(bpre), wg.data_ptr(),
                            ptr<float>(bg), wh.data_ptr(), ptr<float>(bh), ptr<float>(h), ptr<float>(c),
                            ptr<float>(keep), act, ptr<float>(z), n, H, linear ? 1 : 0, (int)mode, bump_ptr(bump),
-                           cur_stream()),
+                           cur_stream(), plan.rows, plan.tile_set, plan.n_tiles, (int)S),
             "dca_actor_core");
 }
 
@@ -518,7 +570,8 @@ void actor_core(torch::Tensor x896, torch::Tensor wpre, torch::Tensor bpre, torc
 // type) with per-channel scales st (6, 128); bt (6, 128).
 std::vector<torch::Tensor> encoder_fp8(torch::Tensor units, torch::Tensor env, torch::Tensor w1, torch::Tensor b1,
                                        torch::Tensor wt, torch::Tensor st, torch::Tensor bt, torch::Tensor we,
-                                       torch::Tensor be, std::vector<int64_t> counts, bool per_unit) {
+                                       torch::Tensor be, std::vector<int64_t> counts, bool per_unit,
+                                       c10::optional<torch::Tensor> rows, c10::optional<torch::Tensor> tile_set) {
   CHECK_DEV(units); CHECK_CONTIG(units); CHECK_F32(env); CHECK_F32(w1); CHECK_F32(b1); CHECK_U8(wt);
   CHECK_F32(st); CHECK_F32(bt); CHECK_F32(we); CHECK_F32(be);
   const bool f16 = units.scalar_type() == at::kHalf;
@@ -526,9 +579,14 @@ std::vector<torch::Tensor> encoder_fp8(torch::Tensor units, torch::Tensor env, t
   TORCH_CHECK(units.dim() == 3 && units.size(2) == 10, "encoder_fp8: units (N, U, 10)");
   const int N = units.size(0), U = units.size(1);
   TORCH_CHECK(env.dim() == 2 && env.size(0) == N && env.size(1) == 3, "encoder_fp8: env (N, 3)");
-  TORCH_CHECK(w1.numel() == 128 * 10 && b1.numel() == 128 && we.numel() == 128 * 3 && be.numel() == 128,
-              "encoder_fp8: W1 (128, 10), W_env (128, 3)");
-  TORCH_CHECK(wt.numel() == 6 * 128 * 128 && st.numel() == 6 * 128 && bt.numel() == 6 * 128,
+  const SetPlan plan = set_plan(rows, tile_set, "encoder_fp8");
+  TORCH_CHECK(!plan || !per_unit, "encoder_fp8: a mixed-weight-set step has no per-unit form");
+  // mixed weight sets: every weight argument carries a leading n_sets dimension
+  const int64_t S = plan ? b1.numel() / 128 : 1;
+  TORCH_CHECK(S >= 1, "encoder_fp8: weight sets");
+  TORCH_CHECK(w1.numel() == S * 128 * 10 && b1.numel() == S * 128 && we.numel() == S * 128 * 3 &&
+              be.numel() == S * 128, "encoder_fp8: W1 (128, 10), W_env (128, 3)");
+  TORCH_CHECK(wt.numel() == S * 6 * 128 * 128 && st.numel() == S * 6 * 128 && bt.numel() == S * 6 * 128,
               "encoder_fp8: W_τ (6, 128, 128) e4m3, scales / biases (6, 128)");
   TORCH_CHECK(counts.size() == 6, "encoder_fp8: six unit counts");
   int c[6];
@@ -540,7 +598,8 @@ std::vector<torch::Tensor> encoder_fp8(torch::Tensor units, torch::Tensor env, t
   auto emb = torch::empty({N, U, 128}, o.dtype(at::kBFloat16));
   hip_check(dca_encoder_fp8(units.data_ptr(), f16 ? 1 : 0, ptr<float>(env), ptr<float>(w1), ptr<float>(b1),
                             wt.data_ptr(), ptr<float>(st), ptr<float>(bt), ptr<float>(we), ptr<float>(be),
-                            ptr<short>(x896), ptr<short>(emb), N, U, c, per_unit ? 1 : 0, cur_stream()),
+                            ptr<short>(x896), ptr<short>(emb), N, U, c, per_unit ? 1 : 0, cur_stream(), plan.rows,
+                            plan.tile_set, plan.n_tiles, (int)S),
             "dca_encoder_fp8");
   return {x896, emb};
 }
@@ -1196,7 +1255,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("encoder_fwd", &encoder_fwd, "fused entity encoder forward (unit MLP, per-type GEMM, max-pool+argmax)",
         py::arg("units"), py::arg("env"), py::arg("w1"), py::arg("b1"), py::arg("wt"), py::arg("bt"), py::arg("we"),
         py::arg("be"), py::arg("counts"), py::arg("compat"), py::arg("exact") = false,
-        py::arg("x896_out") = py::none(), py::arg("emb_out") = py::none(), py::arg("arg_out") = py::none());
+        py::arg("x896_out") = py::none(), py::arg("emb_out") = py::none(), py::arg("arg_out") = py::none(), py::arg("rows") = py::none(),
+        py::arg("tile_set") = py::none());
   m.def("encoder_bwd", &encoder_bwd, "fused entity encoder backward: dW_type (K-blocked split-K MFMA GEMM), dW1, db1",
         py::arg("units"), py::arg("w1"), py::arg("b1"), py::arg("wtT"), py::arg("dtl"), py::arg("q"), py::arg("dx"),
         py::arg("arg"), py::arg("counts"), py::arg("compat"), py::arg("demb_in") = py::none(),
@@ -1221,15 +1281,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("encoder_fp8", &encoder_fp8, "fp8 (e4m3) entity encoder of the actor step: unit MLP, per-type GEMMs, pools "
         "(per_unit: the one-unit-at-a-time workgroup form instead of the wave-parallel one)", py::arg("units"),
         py::arg("env"), py::arg("w1"), py::arg("b1"), py::arg("wt"), py::arg("st"), py::arg("bt"), py::arg("we"),
-        py::arg("be"), py::arg("counts"), py::arg("per_unit") = false);
+        py::arg("be"), py::arg("counts"), py::arg("per_unit") = false, py::arg("rows") = py::none(),
+        py::arg("tile_set") = py::none());
   m.def("actor_core", &actor_core, "fp32 / bf16 actor policy core: pre-RNN + LSTM step (or linear layer) + heads",
         py::arg("x896"), py::arg("wpre"), py::arg("bpre"), py::arg("wg"), py::arg("bg"), py::arg("wh"), py::arg("bh"),
         py::arg("h"), py::arg("c"), py::arg("keep"), py::arg("z"), py::arg("mode"), py::arg("linear") = false,
-        py::arg("active") = py::none(), py::arg("bump") = py::none());
+        py::arg("active") = py::none(), py::arg("bump") = py::none(), py::arg("rows") = py::none(),
+        py::arg("tile_set") = py::none());
   m.def("actor_fp8", &actor_fp8, "fp8 (e4m3) actor policy core: pre-RNN + LSTM step + heads from x896",
         py::arg("x896"), py::arg("wpre"), py::arg("spre"), py::arg("bpre"), py::arg("wg"), py::arg("sg"), py::arg("bg"),
         py::arg("wh"), py::arg("sh"), py::arg("bh"), py::arg("h"), py::arg("c"), py::arg("keep"), py::arg("z"),
-        py::arg("active") = py::none(), py::arg("bump") = py::none());
+        py::arg("active") = py::none(), py::arg("bump") = py::none(), py::arg("rows") = py::none(),
+        py::arg("tile_set") = py::none());
   m.def("attn_block_fwd", &attn_block_fwd, "fused fp32 entity-attention block forward: LN + QKV + attention + "
         "out-projection + residual + pools (-> xn, mean, rstd, qkv, o, lse, e1)");
   m.def("attn_block_bwd", &attn_block_bwd, "fused fp32 entity-attention block backward: demb + dO + attention "

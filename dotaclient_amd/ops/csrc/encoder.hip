@@ -54,6 +54,12 @@ struct FwdParams {
   int N;
   int compat;           // reference bug: eth pool = enh pool (policy.py:127)
   Layout L;
+  // MIX (the actor's slots on different weight sets in one launch, actor/batched.py build_set_plan): row p of the
+  // launch is slot rows[p] (-1: pad), 16-row group t runs on weight set tile_set[t] (-1: unused group); w1, b1, wt,
+  // bt, we, be then hold n_sets sets back to back
+  const int* rows;
+  const int* tile_set;
+  int n_sets;
 };
 
 struct BwdParams {
@@ -93,6 +99,13 @@ __device__ __forceinline__ void load_bfrags(const short* __restrict__ m, bf16x8 
 #pragma unroll
     for (int s = 0; s < 4; ++s)
       bf[n][s] = *reinterpret_cast<const bf16x8*>(m + (size_t)(16 * n + j) * kD + 32 * s + 8 * kg);
+}
+
+// MIX kernels: weight set `set` of an argument that holds the sets back to back (else the argument as it is)
+template <bool MIX, class T>
+__device__ __forceinline__ const T* set_ptr(const T* p, int set, int per_set) {
+  if constexpr (MIX) return p + (size_t)set * per_set;
+  else return p;
 }
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -204,15 +217,24 @@ __device__ __forceinline__ bf16x8 tile_frag(const short* img, int k0, int lane) 
 // fragment read touches). Rows past N load row N-1: their results are never stored and their gradients are zero.
 // (Register-staged conditional loads made the compiler wait out each load before the next: ≈40 serialised round
 // trips per 16-unit job, then most of the encoder's time.)
+template <bool MIX = false>
 __device__ __forceinline__ void stage_units(const float* __restrict__ units, const float* __restrict__ dtl, int U,
-                                            int N, int row0, int ubase, int cc, float* ur, float* dr, int lane) {
+                                            int N, int row0, int ubase, int cc, float* ur, float* dr, int lane,
+                                            const int* __restrict__ rows = nullptr) {
   typedef __attribute__((address_space(1))) void gvoid;
   typedef __attribute__((address_space(3))) void lvoid;
   const int per = cc * kF;                       // floats per row (contiguous in global memory)
   const int nk = (per + 63) >> 6;
 #pragma unroll 4
   for (int r = 0; r < 16; ++r) {
-    const float* src = units + ((size_t)min(row0 + r, N - 1) * U + ubase) * kF;
+    int srow;
+    if constexpr (MIX) {   // the row's slot; pad rows read the group's first slot (never a pad)
+      const int slot = rows[row0 + r];
+      srow = min(max(slot >= 0 ? slot : rows[row0], 0), N - 1);
+    } else {
+      srow = min(row0 + r, N - 1);
+    }
+    const float* src = units + ((size_t)srow * U + ubase) * kF;
     for (int k = 0; k < nk; ++k)
       __builtin_amdgcn_global_load_lds((gvoid*)(src + min(64 * k + lane, per - 1)), (lvoid*)(ur + r * kUP + 64 * k),
                                        4, 0, 0);
@@ -228,6 +250,7 @@ __device__ __forceinline__ void stage_units(const float* __restrict__ units, con
 }
 
 // ============================================================================================================
+template <bool MIX>
 __global__ __launch_bounds__(256, 1) void encoder_fwd_kernel(FwdParams P) {
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
   const int rbase = blockIdx.x * kRows;
@@ -240,18 +263,32 @@ __global__ __launch_bounds__(256, 1) void encoder_fwd_kernel(FwdParams P) {
   // ---- env embedding: relu(We·env + be) → x896[:, 0:128] (32 rows × 128 cols over 256 threads; job 0's workgroups)
   if (blockIdx.y == 0) {
     const int r = tid >> 3, c0 = (tid & 7) * 16;
-    const int row = rbase + r;
+    int row = rbase + r;
+    const float *we = P.we, *be = P.be;
+    if constexpr (MIX) {   // the row's slot and its group's weight set (pad rows / unused groups: nothing stored)
+      const int set = P.tile_set[row >> 4];
+      row = P.rows[row];
+      if (row < 0 || set < 0 || set >= P.n_sets) row = N;
+      else { we += set * kD * 3; be += set * kD; }
+    }
     if (row < N) {
       const float e0 = P.env[row * 3], e1 = P.env[row * 3 + 1], e2 = P.env[row * 3 + 2];
       for (int c = c0; c < c0 + 16; ++c) {
-        const float v = P.be[c] + P.we[c * 3] * e0 + P.we[c * 3 + 1] * e1 + P.we[c * 3 + 2] * e2;
+        const float v = be[c] + we[c * 3] * e0 + we[c * 3 + 1] * e1 + we[c * 3 + 2] * e2;
         x896[(size_t)row * 896 + c] = dca::f2bf(fmaxf(v, 0.f));
       }
     }
   }
 
+  int set = 0;
+  if constexpr (MIX) {
+    // this wave's 16-row group (wv & 1 of the workgroup's two) takes its own weight set; the waves share no barrier,
+    // so a wave whose group is unused simply leaves
+    set = P.tile_set[(rbase >> 4) + (wv & 1)];
+    if (set < 0 || set >= P.n_sets) return;
+  }
   bf16x8 wb[8];
-  load_w1_split(P.w1, P.b1, wb, lane);
+  load_w1_split(set_ptr<MIX>(P.w1, set, kD * kF), set_ptr<MIX>(P.b1, set, kD), wb, lane);
   short* img = &scr[wv][0];
 
   const int i = lane & 15, kg = lane >> 4;
@@ -264,10 +301,11 @@ __global__ __launch_bounds__(256, 1) void encoder_fwd_kernel(FwdParams P) {
     if (cnt == 0) continue;
     const int row0 = rbase + 16 * g;
     bf16x8 wf[8][4];
-    load_bfrags(static_cast<const short*>(P.wt) + (size_t)tau * kD * kD, wf, lane);
+    load_bfrags(set_ptr<MIX>(static_cast<const short*>(P.wt), set, 6 * kD * kD) + (size_t)tau * kD * kD, wf,
+                lane);
     float btv[8];
 #pragma unroll
-    for (int n = 0; n < 8; ++n) btv[n] = P.bt[tau * kD + 16 * n + i];
+    for (int n = 0; n < 8; ++n) btv[n] = set_ptr<MIX>(P.bt, set, 6 * kD)[tau * kD + 16 * n + i];
     f32x4 pmax[8];
     int parg[8][4];
 #pragma unroll
@@ -281,7 +319,7 @@ __global__ __launch_bounds__(256, 1) void encoder_fwd_kernel(FwdParams P) {
      const int cc = min(kStage, cnt - c0);
      // stage the next ≤ kStage units of this job (all loads in flight at once; also drains the W_τ loads)
      __builtin_amdgcn_wave_barrier();
-     stage_units(P.units, nullptr, U, N, row0, uoff + c0, cc, ur, nullptr, lane);
+     stage_units<MIX>(P.units, nullptr, U, N, row0, uoff + c0, cc, ur, nullptr, lane, P.rows);
      __builtin_amdgcn_wave_barrier();
      for (int uc = 0; uc < cc; ++uc) {
       const int u = c0 + uc;
@@ -316,7 +354,11 @@ __global__ __launch_bounds__(256, 1) void encoder_fwd_kernel(FwdParams P) {
       __builtin_amdgcn_wave_barrier();
       // embedding tile → row-major: lane → row i, columns 32s + 8kg … +7 (16-B stores, 64 B contiguous per row)
       {
-        const int row = row0 + i;
+        int row = row0 + i;
+        if constexpr (MIX) {
+          row = P.rows[row];
+          if (row < 0) row = N;
+        }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           const bf16x8 f = tile_frag(img, 32 * s, lane);
@@ -331,7 +373,11 @@ __global__ __launch_bounds__(256, 1) void encoder_fwd_kernel(FwdParams P) {
     for (int n = 0; n < 8; ++n)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int row = row0 + kg * 4 + r;
+        int row = row0 + kg * 4 + r;
+        if constexpr (MIX) {
+          row = P.rows[row];
+          if (row < 0) row = N;
+        }
         if (row < N) {
           const int col = 16 * n + i;
           x896[(size_t)row * 896 + kD + tau * kD + col] = dca::f2bf(pmax[n][r]);
@@ -853,13 +899,24 @@ struct FfParams {
   Layout L;
   int gpj[6];            // row groups per job of each type
   int jbase[7];
+  const int* rows;       // MIX (see FwdParams; the mixed launch plans one row group per job)
+  const int* tile_set;
+  int n_sets;
+  int n_groups;          // MIX: planned row groups (tile_set entries)
 };
 
+template <bool MIX = false>
 __device__ __forceinline__ float ff_stage_load(const FfParams& P, __amdgpu_buffer_rsrc_t Ru, int k, int cnt, int uoff,
                                               int wv, int lane) {
   const int idx = min(64 * min(wv, 2) + lane, 16 * kF - 1);
   const int rb = k / cnt, u = k - rb * cnt;
-  const int row = min(16 * rb + idx / kF, P.N - 1);
+  int row;
+  if constexpr (MIX) {   // the row's slot; pad rows read the group's first slot (never a pad)
+    const int slot = P.rows[16 * rb + idx / kF];
+    row = min(max(slot >= 0 ? slot : P.rows[16 * rb], 0), P.N - 1);
+  } else {
+    row = min(16 * rb + idx / kF, P.N - 1);
+  }
   return bload(Ru, ((row * P.L.U + uoff + u) * kF + idx % kF) * 4);
 }
 
@@ -1056,17 +1113,30 @@ __device__ __forceinline__ void x_put(float* img, int n, const f32x4& v, int i, 
   for (int r = 0; r < 4; ++r) img[(4 * kg + r) * kXP + 16 * n + i] = v[r];
 }
 
+template <bool MIX>
 __global__ __launch_bounds__(512, 1) void encoder_fwd_x_kernel(FfParams P) {
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
   const int i = lane & 15, kg = lane >> 4;
   const int job = blockIdx.x, N = P.N, U = P.L.U;
-  for (int rbase = 32 * job; rbase < N; rbase += 32 * (int)gridDim.x) {     // env embedding (fp32 VALU)
-    const int row = rbase + (tid >> 4), c0 = (tid & 15) * 8;
+  // MIX (the actor's mixed-weight-set launch, FfParams rows / tile_set): the host plans ONE row group per job, so a
+  // job's weights are those of its group's set; rows are gathered from / scattered to their slots
+  const int NR = MIX ? 16 * P.n_groups : N;                                 // rows of the launch (MIX: planned rows)
+  for (int rbase = 32 * job; rbase < NR; rbase += 32 * (int)gridDim.x) {    // env embedding (fp32 VALU)
+    int row = rbase + (tid >> 4);
+    const int c0 = (tid & 15) * 8;
+    const float *we = P.we, *be = P.be;
+    if constexpr (MIX) {   // the row's slot and its group's weight set (pad rows / unused groups: nothing stored)
+      const int p = min(row, NR - 1);
+      const int set = P.tile_set[p >> 4];
+      row = row < NR ? P.rows[p] : -1;
+      if (row < 0 || set < 0 || set >= P.n_sets) row = N;
+      else { we += set * kD * 3; be += set * kD; }
+    }
     if (row < N) {
       const float e0 = P.env[row * 3], e1 = P.env[row * 3 + 1], e2 = P.env[row * 3 + 2];
 #pragma unroll
       for (int c = c0; c < c0 + 8; ++c)
-        P.x896[(size_t)row * 896 + c] = fmaxf(P.be[c] + P.we[c * 3] * e0 + P.we[c * 3 + 1] * e1 + P.we[c * 3 + 2] * e2, 0.f);
+        P.x896[(size_t)row * 896 + c] = fmaxf(be[c] + we[c * 3] * e0 + we[c * 3 + 1] * e1 + we[c * 3 + 2] * e2, 0.f);
     }
   }
   int tau = 0;
@@ -1074,9 +1144,14 @@ __global__ __launch_bounds__(512, 1) void encoder_fwd_x_kernel(FfParams P) {
   for (int t = 1; t < 6; ++t) tau += job >= P.jbase[t] ? 1 : 0;
   if (job >= P.jbase[6]) return;
   const int cnt = P.L.cnt[tau], uoff = P.L.off[tau];
-  const int NB = (N + 15) >> 4;
+  const int NB = MIX ? P.n_groups : (N + 15) >> 4;
   const int g0 = (job - P.jbase[tau]) * P.gpj[tau], g1 = min(g0 + P.gpj[tau], NB);
   const int k0 = g0 * cnt, k1 = g1 * cnt, kl = k1 - 1;
+  int set = 0;
+  if constexpr (MIX) {   // (uniform for the workgroup, before the first barrier) one row group per job: its set
+    set = P.tile_set[g0];
+    if (set < 0 || set >= P.n_sets) return;
+  }
   __shared__ __attribute__((aligned(16))) float img[2][16 * kXP];
   __shared__ __attribute__((aligned(16))) float stg[3][kStg];
 
@@ -1084,23 +1159,31 @@ __global__ __launch_bounds__(512, 1) void encoder_fwd_x_kernel(FfParams P) {
   float wx[32], w1x[3];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {   // B[k = j][n = out] = W_τ[out][j], k = 32s + 8kg + jj
-    const float* p = P.wt + ((size_t)tau * kD + col) * kD + 32 * s + 8 * kg;
+    const float* p = set_ptr<MIX>(P.wt, set, 6 * kD * kD) + ((size_t)tau * kD + col) * kD + 32 * s + 8 * kg;
     const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
     wx[8 * s + 0] = a.x; wx[8 * s + 1] = a.y; wx[8 * s + 2] = a.z; wx[8 * s + 3] = a.w;
     wx[8 * s + 4] = b.x; wx[8 * s + 5] = b.y; wx[8 * s + 6] = b.z; wx[8 * s + 7] = b.w;
   }
-  x_load_w1(P.w1, P.b1, col, kg, w1x);
-  const float btv = P.bt[tau * kD + col];
+  x_load_w1(set_ptr<MIX>(P.w1, set, kD * kF), set_ptr<MIX>(P.b1, set, kD), col, kg, w1x);
+  const float btv = set_ptr<MIX>(P.bt, set, 6 * kD)[tau * kD + col];
   const __amdgpu_buffer_rsrc_t Ru = uniform_rsrc(P.units, N * U * kF * 4),
                                Re = uniform_rsrc(P.emb, N * U * kD * 4);
   f32x4 pmax = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
   int parg[4] = {0, 0, 0, 0};
+  int srow[4] = {0, 0, 0, 0};                   // MIX: slots of this lane's rows 4kg + r of the job's one group
+  if constexpr (MIX) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int slot = P.rows[16 * g0 + 4 * kg + r];
+      srow[r] = slot >= 0 && slot < N ? slot : -1;
+    }
+  }
 
   float pre = 0.f;
   if (wv < 3) {
-    stg[k0 % 3][64 * wv + lane] = ff_stage_load(P, Ru, k0, cnt, uoff, wv, lane);
-    stg[(k0 + 1) % 3][64 * wv + lane] = ff_stage_load(P, Ru, min(k0 + 1, kl), cnt, uoff, wv, lane);
-    pre = ff_stage_load(P, Ru, min(k0 + 2, kl), cnt, uoff, wv, lane);
+    stg[k0 % 3][64 * wv + lane] = ff_stage_load<MIX>(P, Ru, k0, cnt, uoff, wv, lane);
+    stg[(k0 + 1) % 3][64 * wv + lane] = ff_stage_load<MIX>(P, Ru, min(k0 + 1, kl), cnt, uoff, wv, lane);
+    pre = ff_stage_load<MIX>(P, Ru, min(k0 + 2, kl), cnt, uoff, wv, lane);
   }
   lds_barrier();
   {
@@ -1136,14 +1219,17 @@ __global__ __launch_bounds__(512, 1) void encoder_fwd_x_kernel(FfParams P) {
     for (int r = 0; r < 4; ++r) {
       const float v = c[r] + btv;
       if (v > pmax[r]) { pmax[r] = v; parg[r] = u; }
-      const int row = row0 + 4 * kg + r;
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), Re, ((row * U + uoff + u) * kD + col) * 4,
-                                            0, 0);
+      int row = row0 + 4 * kg + r;
+      if constexpr (MIX) row = srow[r];
+      // (MIX pad rows: an offset past the resource's end, like the rows past N: dropped)
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), Re,
+                                            MIX && row < 0 ? 0x7ffffff0 : ((row * U + uoff + u) * kD + col) * 4, 0, 0);
     }
     if (u == cnt - 1) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int row = row0 + 4 * kg + r;
+        int row = row0 + 4 * kg + r;
+        if constexpr (MIX) row = srow[r] < 0 ? N : srow[r];
         if (row < N) {
           P.x896[(size_t)row * 896 + kD + tau * kD + col] = pmax[r];
           P.arg[((size_t)row * 6 + tau) * kD + col] = (unsigned char)parg[r];
@@ -1152,7 +1238,7 @@ __global__ __launch_bounds__(512, 1) void encoder_fwd_x_kernel(FfParams P) {
         parg[r] = 0;
       }
     }
-    if (wv < 3) pre = ff_stage_load(P, Ru, min(k + 3, kl), cnt, uoff, wv, lane);
+    if (wv < 3) pre = ff_stage_load<MIX>(P, Ru, min(k + 3, kl), cnt, uoff, wv, lane);
     buf ^= 1;
   }
 }
@@ -1476,8 +1562,14 @@ __global__ __launch_bounds__(256) void dwt_reduce(const float* __restrict__ part
 extern "C" hipError_t dca_encoder_fwd(const float* units, const float* env, const float* w1, const float* b1,
                                       const void* wt, const float* bt, const float* we, const float* be, void* x896,
                                       void* emb, unsigned char* arg, int N, int U, const int* counts, int compat,
-                                      hipStream_t st, int f32) {
-  FwdParams P{units, env, w1, b1, wt, bt, we, be, x896, emb, arg, N, compat, {}};
+                                      hipStream_t st, int f32, const int* rows, const int* tile_set, int n_tiles,
+                                      int n_sets) {
+  const bool mix = rows != nullptr;
+  // mixed weight sets (the actor step): the bf16 kernel (two 16-row groups per workgroup: an even tile count) and the
+  // exact fp32 kernel
+  if (mix && (tile_set == nullptr || n_tiles < 1 || n_sets < 1 || f32 == 1 || (f32 == 0 && (n_tiles & 1))))
+    return hipErrorInvalidValue;
+  FwdParams P{units, env, w1, b1, wt, bt, we, be, x896, emb, arg, N, compat, {}, rows, tile_set, n_sets};
   P.L.U = U;
   int acc = 0;
   for (int t = 0; t < 6; ++t) { P.L.cnt[t] = counts[t]; P.L.off[t] = acc; acc += counts[t]; }
@@ -1486,25 +1578,27 @@ extern "C" hipError_t dca_encoder_fwd(const float* units, const float* env, cons
   // rows) still fill the 256 CUs, and heavy jobs (16-unit types, dispatched first) are balanced by the light ones
   if (f32) {
     FfParams F{units, env, w1, b1, static_cast<const float*>(wt), bt, we, be, static_cast<float*>(x896),
-               static_cast<float*>(emb), arg, N, P.L, {}, {}};
-    const long long NB = (N + 15) / 16;
+               static_cast<float*>(emb), arg, N, P.L, {}, {}, rows, tile_set, n_sets, n_tiles};
+    const long long NB = mix ? n_tiles : (N + 15) / 16;
     long long total = 0;
     for (int t = 0; t < 6; ++t) total += counts[t] * NB;
     const long long target = std::max<long long>(1, (total + 499) / 500);   // ≈500 equal jobs (cf. fb_plan)
     int jobs = 0;
     for (int t = 0; t < 6; ++t) {
       F.jbase[t] = jobs;
-      F.gpj[t] = (int)((target + std::max(1, counts[t]) - 1) / std::max(1, counts[t]));
+      F.gpj[t] = mix ? 1 : (int)((target + std::max(1, counts[t]) - 1) / std::max(1, counts[t]));
       if (counts[t] > 0) jobs += (int)((NB + F.gpj[t] - 1) / F.gpj[t]);
     }
     F.jbase[6] = jobs;
     // every launch also covers the env embedding (32-row blocks strided over the grid)
-    if (f32 == 2) encoder_fwd_x_kernel<<<std::max(jobs, 1), 512, 0, st>>>(F);
+    if (mix) encoder_fwd_x_kernel<true><<<std::max(jobs, 1), 512, 0, st>>>(F);
+    else if (f32 == 2) encoder_fwd_x_kernel<false><<<std::max(jobs, 1), 512, 0, st>>>(F);
     else encoder_fwd_f32_items_kernel<<<std::max(jobs, 1), 512, 0, st>>>(F);
     return hipGetLastError();
   }
-  const dim3 grid((N + kRows - 1) / kRows, kJobs);
-  encoder_fwd_kernel<<<grid, 256, 0, st>>>(P);
+  const dim3 grid(mix ? n_tiles / 2 : (N + kRows - 1) / kRows, kJobs);
+  if (mix) encoder_fwd_kernel<true><<<grid, 256, 0, st>>>(P);
+  else encoder_fwd_kernel<false><<<grid, 256, 0, st>>>(P);
   return hipGetLastError();
 }
 

@@ -25,11 +25,13 @@ hipError_t dca_attn_block_bwd_f32(const float* dtl, const float* q, int ldq, con
 hipError_t dca_actor_fp8(const short* x896, const void* wpre, const float* spre, const float* bpre, const void* wg,
                          const float* sg, const float* bg, const void* wh, const float* sh, const float* bh, float* h,
                          float* c, const float* keep, const float* active, float* z, int n, long long* bump,
-                         hipStream_t stream);
+                         hipStream_t stream, const int* rows = nullptr, const int* tile_set = nullptr,
+                         int n_tiles = 0, int n_sets = 1);
 hipError_t dca_encoder_fp8(const void* units, int f16, const float* env, const float* w1, const float* b1,
                            const void* wt, const float* st, const float* bt, const float* we, const float* be,
                            short* x896, short* emb, int N, int U, const int* counts, int per_unit,
-                           hipStream_t stream);
+                           hipStream_t stream, const int* rows = nullptr, const int* tile_set = nullptr,
+                           int n_tiles = 0, int n_sets = 1);
 
 hipError_t dca_dpre_dx(const float* dG, const void* w1h, const void* w1l, const float* x, const void* w2h,
                        const void* w2l, float* dpre, float* dx, int N, int K1, int X, int exact, int epi, hipStream_t stream);
@@ -56,7 +58,9 @@ hipError_t dca_heads_loss(const float* z, int ldz, const void* emb, const unsign
 
 hipError_t dca_encoder_fwd(const float* units, const float* env, const float* w1, const float* b1, const void* wt,
                            const float* bt, const float* we, const float* be, void* x896, void* emb,
-                           unsigned char* arg, int N, int U, const int* counts, int compat, hipStream_t st, int f32);
+                           unsigned char* arg, int N, int U, const int* counts, int compat, hipStream_t st, int f32,
+                           const int* rows = nullptr, const int* tile_set = nullptr, int n_tiles = 0,
+                           int n_sets = 1);
 size_t dca_encoder_bwd_workspace(int N, int U, const int* counts, int f32);
 hipError_t dca_encoder_bwd(const float* units, const float* w1, const float* b1, const void* wtT, const float* dtl,
                            const float* q, int ldq, const float* dx, const unsigned char* arg, float* dwt, float* dw1,
@@ -83,7 +87,8 @@ hipError_t dca_sample_actions(const float* z, int ldz, const void* emb, int emb_
 hipError_t dca_actor_core(const void* x896, int x_f32, const void* wpre, const float* bpre, const void* wg,
                           const float* bg, const void* wh, const float* bh, float* h, float* c, const float* keep,
                           const float* active, float* z, int n, int hidden, int linear, int mode, long long* bump,
-                          hipStream_t st);
+                          hipStream_t st, const int* rows = nullptr, const int* tile_set = nullptr, int n_tiles = 0,
+                          int n_sets = 1);
 hipError_t dca_actor_state_prep(const short* pre, float* h, float* c, const float* keep, short* xh, int N, int P,
                                 int H, long long* bump, hipStream_t st);
 hipError_t dca_lstm_cell(const float* gates, float* h, float* c, short* h16, const float* active, int N, int H,
