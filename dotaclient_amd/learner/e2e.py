@@ -90,9 +90,11 @@ def measure_e2e(model: str = 'lstm512', device='cuda', duration: float = 20.0, g
         loader.shutdown(wait=True)
         if log_dir is None:
             shutil.rmtree(tmp, ignore_errors=True)
-    return _summary(rows, wall, actor_steps, dropped, games, dict(
+    out = _summary(rows, wall, actor_steps, dropped, games, dict(
         batch_size=batch_size, seq_len=seq_len, seq_per_epoch=seq_per_epoch, epochs=epochs, rollout_size=rollout_size,
         max_dota_time=max_dota_time, precision=precision, prefetch_rollouts=prefetch, actor='thread'))
+    out.update(_team_window())
+    return out
 
 
 def _learner_loop(opt, duration, warmup_iterations, max_iterations, counters, check, agree=None):
@@ -102,6 +104,7 @@ def _learner_loop(opt, duration, warmup_iterations, max_iterations, counters, ch
     from .optimizer import DotaOptimizer
     rows = []
     _learner_loop.metrics = {}
+    _learner_loop.team = {}
     it = opt.iteration_start
     for _ in range(warmup_iterations):
         opt.run_iteration(it)
@@ -134,6 +137,7 @@ def _learner_loop(opt, duration, warmup_iterations, max_iterations, counters, ch
                 acc = _learner_loop.metrics.setdefault(k, [0.0, 0])
                 acc[0] += float(v)
                 acc[1] += 1
+        _team_add(_learner_loop.team, m)
         e = check()
         if e:
             raise e
@@ -143,6 +147,32 @@ def _learner_loop(opt, duration, warmup_iterations, max_iterations, counters, ch
     c1 = counters()
     opt.flush_metrics()            # the last iteration's deferred metrics / logs (outside the timed window)
     return rows, wall, (c1[0] - c0[0], c1[1] - c0[1])
+
+
+def _team_add(acc, m):
+    """Fold one iteration's ``team/*`` metrics (learner/optimizer.py ``_team_metrics``) into the window's totals."""
+    if 'team/launches' not in m:
+        return
+    for k, src in (('launches', 'team/launches'), ('degraded', 'team/degraded'), ('aborted', 'team/aborted'),
+                   ('absent', 'team/absent')):
+        acc[k] = acc.get(k, 0) + int(m[src])
+    for kind in ('fwd', 'bwd'):
+        # the iteration means weigh alike: every iteration makes the same number of calls of each kind
+        acc[kind + '_sum'] = acc.get(kind + '_sum', 0.0) + float(m[f'team/{kind}_ms'])
+        acc[kind + '_max'] = max(acc.get(kind + '_max', 0.0), float(m[f'team/{kind}_ms_max']))
+    acc['n'] = acc.get('n', 0) + 1
+
+
+def _team_window(acc=None):
+    """The recurrence telemetry of the measured window as result fields (empty without the fused GPU backend): did
+    every XCD team form, and the device time per recurrence call."""
+    acc = getattr(_learner_loop, 'team', {}) if acc is None else acc
+    if not acc.get('n'):
+        return {}
+    return {'team_launches': acc['launches'], 'team_degraded_launches': acc['degraded'],
+            'team_aborted': acc['aborted'], 'team_absent': acc['absent'],
+            'recurrence_fwd_ms': acc['fwd_sum'] / acc['n'], 'recurrence_bwd_ms': acc['bwd_sum'] / acc['n'],
+            'recurrence_fwd_ms_max': acc['fwd_max'], 'recurrence_bwd_ms_max': acc['bwd_max']}
 
 
 def _summary(rows, wall, actor_steps, dropped, games, config):
@@ -169,6 +199,7 @@ def _summary(rows, wall, actor_steps, dropped, games, config):
         'learner_gpu_ms_per_step': float(np.nanmean(a[:, 10])) if n_it and np.isfinite(a[:, 10]).any() else float('nan'),
         # the slowest iteration's steps (a device-wide stall — queue preemption, memory eviction — shows here)
         'learner_gpu_ms_per_step_max': float(np.nanmax(a[:, 10])) if n_it and np.isfinite(a[:, 10]).any() else float('nan'),
+        'learner_gpu_ms_per_step_p99': float(np.nanpercentile(a[:, 10], 99)) if n_it and np.isfinite(a[:, 10]).any() else float('nan'),
         'rollouts_consumed': int(np.nansum(a[:, 11])) if n_it else 0,
         # the stager thread per iteration: packing + upload issue, and waiting for the decoded rollouts
         'stage_ms_per_iteration': 1e3 * float(np.nanmean(a[:, 12])) if n_it and np.isfinite(a[:, 12]).any() else float('nan'),
@@ -538,6 +569,7 @@ def measure_e2e_node(model: str = 'lstm512', device='cuda', duration: float = 20
     mine['ingest_decode'] = ingest_diag          # decode threads over the window (claims, waits, decode seconds)
     mine['actor_gpu_busy_steps_per_s'] = gpu_busy
     mine['learner_metrics'] = {k: a / max(n, 1) for k, (a, n) in getattr(_learner_loop, 'metrics', {}).items()}
+    mine.update(_team_window())
     mine['report'] = extra
     per_rank = [mine]
     if pdist.is_distributed():
@@ -554,6 +586,9 @@ def measure_e2e_node(model: str = 'lstm512', device='cuda', duration: float = 20
     out['rollouts_consumed_per_rank'] = cons
     out['consumption_skew'] = (max(cons) / max(1, min(cons))) if cons else float('nan')
     out['learner_gpu_ms_per_step_per_rank'] = [r.get('learner_gpu_ms_per_step') for r in per_rank]
+    if 'team_launches' in mine:
+        for k in ('team_degraded_launches', 'recurrence_fwd_ms_max', 'recurrence_bwd_ms_max'):
+            out[k + '_per_rank'] = [r.get(k) for r in per_rank]
     reports = [r.pop('report') for r in per_rank]
     out.pop('report', None)
     if report is not None:

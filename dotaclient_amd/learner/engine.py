@@ -421,6 +421,13 @@ class Learner:
             flags.append(self.model.err)
         return flags
 
+    def team_stat_tensors(self) -> List[torch.Tensor]:
+        """The recurrence's device statistics blocks (ops/lstm.py; empty on the torch backend), for a caller that
+        snapshots them asynchronously with its other per-iteration values."""
+        if self.backend != 'fused' or self.device.type != 'cuda':
+            return []
+        return self.model.team_stat_tensors()
+
     def _finish(self, vec):
         metrics = self._metrics_from_vec(vec.clone())
         # a copy: the optimizer's norm is ONE persistent tensor rewritten by every step, and with deferred metrics the

@@ -983,8 +983,63 @@ class DotaOptimizer:
             buf[i] = torch.empty(max(vec.numel(), 2 * buf[i].numel()), dtype=torch.float32).pin_memory()
         h = buf[i][:vec.numel()]
         h.copy_(vec, non_blocking=True)
+        # the recurrence's telemetry blocks ride along as INTEGERS (their running totals pass 2^24, the float32
+        # vector's exact range, within hours): one int32 concatenation into its own pair of pinned buffers
+        team = None
+        blocks = self.learner.team_stat_tensors()
+        if blocks:
+            tv = torch.cat([b.reshape(-1) for b in blocks])
+            tbuf = self.__dict__.setdefault('_host_team_bufs', [None, None])
+            if tbuf[i] is None or tbuf[i].numel() != tv.numel():
+                tbuf[i] = torch.empty(tv.numel(), dtype=torch.int32).pin_memory()
+            tbuf[i].copy_(tv, non_blocking=True)
+            team = (tbuf[i], len(blocks))
         return dict(vec=h, n_loss=sum(x.numel() for x in losses), keys=keys, seg=seg, n_ema=n_ema,
-                    ema_shape=tuple(ema_snap.shape) if ema_snap is not None else None, n_flags=len(flags))
+                    ema_shape=tuple(ema_snap.shape) if ema_snap is not None else None, n_flags=len(flags),
+                    team=team)
+
+    def _team_metrics(self, blocks, it) -> Dict[str, float]:
+        """The ``team/*`` metrics of one iteration from host copies of the recurrence's statistics blocks
+        (ops/lstm.py): counts and means from the change of the running totals since the previous iteration, maxima
+        from the ring records with a new ``seq``. (The first iteration also counts the launches made before it, the
+        capture's warm-up steps.) Logs one warning line when a launch of the iteration was degraded."""
+        from ..ops.lstm import STAT_KINDS, merge_team_stats, parse_team_stats
+        parsed = [parse_team_stats(b) for b in blocks]
+        cur = merge_team_stats(parsed)
+        prev = self.__dict__.get('_team_prev')
+        seqs = [p['seq'] for p in parsed]
+        prev_seqs = prev['seqs'] if prev is not None and len(prev['seqs']) == len(seqs) else [0] * len(seqs)
+        zero = dict(launches=0, degraded=0, aborted=0, absent=0, ticks=0)
+        d = {k: {f: cur[k][f] - (prev['tot'][k][f] if prev is not None else zero[f]) for f in zero}
+             for k in STAT_KINDS}
+        new = [r for r in cur['records'] if r['seq'] > prev_seqs[r['block']]]
+        lost = sum(max(0, (s - s0) - sum(1 for r in new if r['block'] == i))
+                   for i, (s, s0) in enumerate(zip(seqs, prev_seqs)))
+        self._team_prev = dict(seqs=seqs, tot={k: {f: cur[k][f] for f in zero} for k in STAT_KINDS})
+
+        def ms_max(kind, key='ms'):
+            return max([r[key] for r in new if kind is None or r['kind'] == kind], default=0.0)
+
+        out = {'team/launches': float(d['fwd']['launches'] + d['bwd']['launches']),
+               'team/degraded': float(d['fwd']['degraded'] + d['bwd']['degraded']),
+               'team/aborted': float(d['fwd']['aborted'] + d['bwd']['aborted']),
+               'team/absent': float(d['fwd']['absent'] + d['bwd']['absent']),
+               'team/fwd_ms': d['fwd']['ticks'] / 1e5 / max(1, d['fwd']['launches']),
+               'team/bwd_ms': d['bwd']['ticks'] / 1e5 / max(1, d['bwd']['launches']),
+               'team/fwd_ms_max': ms_max('fwd'), 'team/bwd_ms_max': ms_max('bwd'),
+               'team/queue_ms_max': ms_max(None, 'queue_ms'), 'team/records_lost': float(lost)}
+        if out['team/degraded'] > 0:                    # (one line per iteration, however many launches)
+            bad = [r for r in new if r['degraded']]
+            if bad:
+                w = max(bad, key=lambda r: r['ms'])
+                logger.warning('it=%d: %d degraded recurrence launch(es) — a team ran more than its share of chains; '
+                               'slowest: %s seq %d, %.3f ms, XCDs aborted %s absent %s, chains %s', it,
+                               int(out['team/degraded']), w['kind'], w['seq'], w['ms'], w['aborted'], w['absent'],
+                               w['chains'])
+            else:
+                logger.warning('it=%d: %d degraded recurrence launch(es), their records already left the ring', it,
+                               int(out['team/degraded']))
+        return out
 
     def _defer_metrics(self) -> bool:
         return self._pipelined() and self.cfg.defer_metrics and self.cfg.async_checkpoint
@@ -1081,6 +1136,16 @@ class DotaOptimizer:
             metrics[f'entropy/{k}'] = mean[f'entropy/{k}']
         for k, v in reward_dict.items():
             metrics[f'reward_per_sec/{k}'] = float(v)
+        # the recurrence's telemetry (fused backend on a GPU only): from the pinned snapshot, or — when this iteration
+        # is finalised synchronously anyway — from a copy of the device blocks
+        team_blocks = None
+        if hs is not None and hs.get('team') is not None:
+            tv, nb = hs['team']
+            team_blocks = list(tv.numpy().copy().reshape(nb, -1))
+        elif hs is None:
+            team_blocks = [b.cpu().numpy() for b in self.learner.team_stat_tensors()]
+        if team_blocks:
+            metrics.update(self._team_metrics(team_blocks, it))
         metrics.update(self.timer.pop())
         logger.info('it=%d steps_per_s=%.1f avg_weight_age=%.1f reward_per_sec=%.4f loss=%.4f entropy=%.3f', it,
                     steps_per_s, metrics['avg_weight_age'], metrics['reward_per_sec/sum'], metrics['loss/sum'],

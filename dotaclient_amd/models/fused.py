@@ -302,6 +302,12 @@ class FusedPolicy:
                 metrics[k] = st[i] / st[3].clamp_min(1.0)
         return loss, metrics
 
+    def team_stat_tensors(self) -> List[torch.Tensor]:
+        """The device telemetry blocks of this model's recurrence launches (ops/lstm.py ``parse_team_stats``), for the
+        learner's asynchronous per-iteration snapshot. None yet: the kernels do not write one
+        (profiles/team_telemetry.md)."""
+        return list(self.__dict__.get('_team_blocks', []))
+
     def check_error(self):
         """Raise if a persistent kernel timed out (host sync — call at iteration boundaries, not per step)."""
         e = int(self.err.item())
