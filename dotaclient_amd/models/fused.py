@@ -41,8 +41,6 @@ import torch
 
 from .policy import Policy
 
-LDZ = 160
-
 
 class FusedPolicy:
     def __init__(self, policy: Policy, loss_cfg=None, precision: str = 'fp32'):
@@ -66,11 +64,6 @@ class FusedPolicy:
         # the 5v5 entity-attention encoder has fused kernels on the pipelined (time-major) step only
         self.attention_fused = (self.cfg.entity_attention and self.cfg.unit_dim == 128 and self.cfg.env_dim == 128
                                 and self.cfg.attention_heads == 4 and self.cfg.layout.max_units == 64)
-
-    def wcast(self, t: torch.Tensor) -> torch.Tensor:
-        """A detached working copy of a weight in this learner's GEMM operand dtype (fp32 or bf16)."""
-        t = t.detach()
-        return t if self.fp32 else t.to(torch.bfloat16)
 
     def apply_direct_grads(self, grads, g, written=(), set_mask: bool = True):
         """Accumulate precomputed gradients straight into the parameters' ``.grad`` (views of the learner's flat
@@ -96,8 +89,8 @@ class FusedPolicy:
 
     # ---- direct (autograd-free) learner step support ---------------------------------------------
     def attach_flat(self, flat: torch.Tensor):
-        """The learner's flat fp32 parameter buffer (every parameter is a view of it): the per-step weight images
-        are gathered from it by one kernel (models/pipelined.py:WeightImages)."""
+        """The learner's flat fp32 parameter buffer (every parameter is a view of it): the weight operands the step
+        reads at this precision are gathered from it by one kernel (models/pipelined.py:WeightImages)."""
         self.flat_buffer = flat
         self._wimg = None
 
@@ -109,7 +102,9 @@ class FusedPolicy:
         if getattr(self, '_wimg', None) is None or self._wimg_key != key:
             if getattr(self, 'flat_buffer', None) is None:
                 raise RuntimeError('FusedPolicy.attach_flat(flat) must be called before the fused LSTM step')
-            self._wimg = WeightImages(self, self.flat_buffer, with_value)
+            lstm = self.cfg.rnn == 'lstm'
+            self._wimg = WeightImages(self.cfg, zip(self.param_names, self.params), self.flat_buffer, self.precision,
+                                      with_value, self.gate_perm(self.cfg.hidden, 'cpu') if lstm else None)
             self._wimg_key = key
         return self._wimg
 
@@ -179,8 +174,6 @@ class FusedPolicy:
         if getattr(self, '_perm_key', None) != key:
             from ..ops.lstm import gate_perm
             self._perm, self._perm_key = gate_perm(H, device), key
-            self._inv = torch.empty_like(self._perm)
-            self._inv[self._perm] = torch.arange(self._perm.numel(), device=self._perm.device)
         return self._perm
 
     def gate_perm_i32(self, H, device):
@@ -189,11 +182,6 @@ class FusedPolicy:
         if getattr(self, '_perm32_key', None) != key:
             self._perm32, self._perm32_key = self.gate_perm(H, device).to(torch.int32).contiguous(), key
         return self._perm32
-
-    def gate_inv(self, H, device):
-        """Inverse of :meth:`gate_perm` (unit-major gate rows → PyTorch gate-major rows), cached."""
-        self.gate_perm(H, device)
-        return self._inv
 
     def type_segments(self, device):
         """(U, 6) 0/1 matrix mapping unit slots to their unit type (sums pointer gradients per type), cached."""
@@ -233,25 +221,6 @@ class FusedPolicy:
         self.params = [p for _, p in self.policy.named_parameters()]
 
     # ------------------------------------------------------------------------------------------------
-    def head_cat(self, P, differentiable: bool = False):
-        """Concatenate the five head Linear layers into one (LDZ, H) matrix: [q | enum | x | y | value | pad].
-        ``differentiable`` keeps the autograd link to the parameters (per-stage path); the fully fused Function
-        computes the head gradients itself and uses detached copies."""
-        H = self.cfg.hidden
-        dev = P['affine_value.weight'].device
-        d = (lambda t: t) if differentiable else (lambda t: t.detach())
-        with_value = self.loss_cfg is None or self.loss_cfg.vf_coef > 0
-        wv = d(P['affine_value.weight']) if with_value else torch.zeros(1, H, device=dev)
-        bv = d(P['affine_value.bias']) if with_value else torch.zeros(1, device=dev)
-        pad = LDZ - 150
-        w = torch.cat([d(P['affine_unit_attention.weight']), d(P['affine_head_enum.weight']),
-                       d(P['affine_move_x.weight']), d(P['affine_move_y.weight']), wv,
-                       torch.zeros(pad, H, device=dev)], 0)
-        b = torch.cat([d(P['affine_unit_attention.bias']), d(P['affine_head_enum.bias']),
-                       d(P['affine_move_x.bias']), d(P['affine_move_y.bias']), bv,
-                       torch.zeros(pad, device=dev)], 0)
-        return w, b
-
     def split_head_grads(self, dW, db, grads):
         spans = [('affine_unit_attention', 0, 128), ('affine_head_enum', 128, 131), ('affine_move_x', 131, 140),
                  ('affine_move_y', 140, 149)]

@@ -9,8 +9,9 @@ weight-gradient GEMMs on the side stream; everything else on the main stream); t
   ``backward`` only scales the precomputed gradients by the upstream gradient (used by ``Learner.loss`` callers
   that backprop themselves, and by tests);
 * :func:`train_direct` — the learner's hot path: time-major inputs (gathered straight from the HBM replay,
-  ``learner.engine.Learner.train_step_replay``), loss normalisers from one kernel (``loss_prep``), the per-step
-  working copies of all weights from one gather kernel (``weight_prep``, :class:`WeightImages`), gradients written
+  ``learner.engine.Learner.train_step_replay``), loss normalisers from one kernel (``loss_prep``), the weight
+  operands the step reads at its precision from one gather kernel (``weight_prep``, :class:`WeightImages`, which
+  alone decides each operand's form: the step passes ``W[role]`` on as it is), gradients written
   into the flat gradient buffer by one multi-tensor kernel and the loss + metrics by one kernel
   (``loss_assemble``) — about 120 fewer launches per step than the autograd route, and the whole step is
   capturable in one hipGraph.
@@ -59,22 +60,86 @@ def _k16_order(w: torch.Tensor) -> torch.Tensor:
     return w.view(R // 16, 4, 4, K // 16, 16).permute(0, 3, 1, 4, 2).contiguous()
 
 
+def _slab_major(w: torch.Tensor) -> torch.Tensor:
+    """(R, K) → slab-major [K/32][R][32]: a wave's weight load of the chain kernels is 1 KB contiguous
+    (ops/csrc/dx_chain.hip)."""
+    R, K = w.shape
+    return w.reshape(R, K // 32, 32).permute(1, 0, 2).contiguous()
+
+
+# Forms of a weight operand. F32: fp32 gather; SUM: fp32 sum of two sources. The MFMA weight operands are (hi, lo)
+# pairs in the order their kernel loads them — bf16 hi / lo images (x = hi + lo) at fp32, the fp32 image and an empty
+# lo at fp32-exact: MAT a matrix of the chain kernels (slab-major hi / lo, or the fp32 matrix as it is), FRAG / K16 the
+# attention block's fragment orders (the same order at both precisions).
+F32, SUM, MAT, FRAG, K16 = 'f32', 'sum', 'mat', 'frag', 'k16'
+# form → (image order of the hi / lo pair, image order of the exact fp32 operand)
+_ORDER = {MAT: (_slab_major, torch.Tensor.contiguous), FRAG: (_frag_order, _frag_order), K16: (_k16_order, _k16_order)}
+
+
+def _operand_table(cfg, idx, perm, with_value: bool):
+    """(role, source index expression, form) of every weight operand the fused step reads. ``idx(name)``: the flat
+    buffer indices of a parameter, in its shape; −1 = a zero. Roles are named for what they feed."""
+    H = cfg.hidden
+    lstm = cfg.rnn == 'lstm'
+    neg = lambda *shape: torch.full(shape, -1, dtype=torch.int64)  # noqa: E731
+    wt = torch.stack([idx(f'affine_unit_{s}.weight') for s in TYPE_SUFFIX])
+    bt = torch.stack([idx(f'affine_unit_{s}.bias') for s in TYPE_SUFFIX])
+    wpre = idx('affine_pre_rnn.weight')
+    # the recurrent layer's input weight: W_ih (rows in unit-major gate order) or the reference's linear fake_rnn W_f
+    # (policy.py:67-68, 143-145)
+    w_in = idx('rnn.weight_ih_l0')[perm] if lstm else idx('fake_rnn.weight')
+    # W_cat = [attention | enum | x | y | value | 0-pad], zero-padded to the 256 rows of the chain kernel's stage
+    heads = ('affine_unit_attention', 'affine_head_enum', 'affine_move_x', 'affine_move_y')
+    wv, bv = (idx('affine_value.weight'), idx('affine_value.bias')) if with_value else (neg(1, H), neg(1))
+    wcat = torch.cat([idx(f'{h}.weight') for h in heads] + [wv, neg(256 - 150, H)], 0)
+    bcat = torch.cat([idx(f'{h}.bias') for h in heads] + [bv, neg(256 - 150)])
+    enc_b = ('enc_b', bt, F32)
+    if cfg.entity_attention:
+        # 5v5: the encoder adds b_τ + b_out (E0' = E0 + b_out; LayerNorm subtracts it again and the out-projection
+        # then accumulates onto E0' in place: no residual copy, no bias pass)
+        wq, wo, bo = idx('entity_attn.qkv.weight'), idx('entity_attn.out.weight'), idx('entity_attn.out.bias')
+        enc_b = ('enc_b', (bt, bo.unsqueeze(0).expand(6, -1)), SUM)
+    rows = [
+        ('enc_w', wt, F32),                             # encoder: (6, 128, 128) type weights
+        ('enc_wT', wt.transpose(1, 2), F32),            # encoder backward: their transposes
+        enc_b,                                          # (6, 128)
+        ('pre_w', wpre, MAT),                           # forward chain: W_pre (256, 896)
+        ('pre_b', idx('affine_pre_rnn.bias'), F32),
+        ('in_w', w_in, MAT),                            # forward chain: W_ih (4H, 256) / W_f (H, 256)
+        ('heads_w', wcat, MAT),                         # heads GEMM: W_cat (256, H)
+        ('heads_b', bcat, F32),
+        ('heads_wT', wcat.t(), MAT),                    # ∂h = ∂z·W_cat
+        ('dx_in_wT', w_in.t(), MAT),                    # ∂X chain: ∂pre = ∂G·W_ih, K-contiguous per column
+        ('dx_pre_wT', wpre.t(), MAT),                   # ∂X chain: ∂x896 = ∂pre·W_pre
+    ]
+    if lstm:
+        rows += [('rec_w', idx('rnn.weight_hh_l0'), F32),      # recurrence: W_hh (4H, H), PyTorch's row order
+                 ('rec_b', (idx('rnn.bias_ih_l0')[perm], idx('rnn.bias_hh_l0')[perm]), SUM)]   # unit-major (4H)
+    else:
+        rows += [('rec_b', idx('fake_rnn.bias'), F32)]
+    if cfg.entity_attention:
+        rows += [('attn_out_b', bo, F32),
+                 ('attn_qkv_w', wq, FRAG), ('attn_out_w', wo, FRAG),            # attention block forward
+                 ('attn_out_wT', wo.t().contiguous(), FRAG), ('attn_qkv_k16', wq, K16)]   # and backward
+    return rows
+
+
 class WeightImages:
     """Per-step working copies of the weights, produced by ONE ``weight_prep`` gather launch from the flat fp32
-    parameter buffer (instead of ≈25 cast / stack / permute / cat launches):
+    parameter buffer (instead of ≈25 cast / stack / permute / cat launches), and the only place that knows which form
+    a kernel's weight operand takes at ``precision`` ('fp32' = bf16x3, 'fp32-exact'): :func:`_operand_table` names the
+    operands, :meth:`refresh` returns role → fp32 tensor, or → the ready (hi, lo) argument pair of an MFMA operand.
+    Only what the step reads at that precision is gathered. The index maps are built once, from the parameters' offsets
+    in the flat buffer; ``perm``: the gate permutation (ops/lstm.py ``gate_perm``, on the CPU) of an LSTM policy."""
 
-    GEMM operands (fp32; the historical ``16`` suffix of the keys is kept): ``wt16`` (6,128,128) type
-    weights, ``wtT16`` their transposes, ``wpre16`` (256,896) + ``bpre16``, ``wih16`` (4H,256) rows in unit-major
-    gate order, ``whh16`` (4H,H), ``wcat16`` (LDZ,H) = [attention|enum|x|y|value|0-pad];
-    always fp32: ``bt`` (6,128), ``bias4`` (4H) = (b_ih + b_hh) in unit-major gate order, ``bcat`` (LDZ).
-    The index maps are built once from the parameters' offsets in the flat buffer."""
-
-    def __init__(self, fp, flat: torch.Tensor, with_value: bool):
-        cfg = fp.cfg
-        H = cfg.hidden
+    def __init__(self, cfg, named_params, flat: torch.Tensor, precision: str, with_value: bool,
+                 perm: Optional[torch.Tensor] = None):
+        if precision not in ('fp32', 'fp32-exact'):
+            raise ValueError(f'the fused step runs at fp32 / fp32-exact, not {precision!r}')
+        exact = precision == 'fp32-exact'
         dev = flat.device
         base = flat.data_ptr()
-        P = dict(zip(fp.param_names, fp.params))
+        P = dict(named_params)
 
         def idx(name):
             p = P[name]
@@ -83,125 +148,42 @@ class WeightImages:
             assert 0 <= off and off + p.numel() <= flat.numel(), f'{name} is not a view of the flat buffer'
             return torch.arange(p.numel(), dtype=torch.int64).view(p.shape) + off
 
-        lstm = cfg.rnn == 'lstm'
-        perm = fp.gate_perm(H, 'cpu') if lstm else None
-        neg = lambda *shape: torch.full(shape, -1, dtype=torch.int64)  # noqa: E731
-        # the recurrent layer's input weight — W_ih (rows in unit-major gate order) or the reference's linear fake_rnn
-        # W_f (policy.py:67-68, 143-145) — keeps the keys wih16 / wihT16 / ih_s / dx1_s for both
-        w_in = idx('rnn.weight_ih_l0')[perm] if lstm else idx('fake_rnn.weight')
-        wt = torch.stack([idx(f'affine_unit_{s}.weight') for s in TYPE_SUFFIX])
-        head_rows = [idx('affine_unit_attention.weight'), idx('affine_head_enum.weight'),
-                     idx('affine_move_x.weight'), idx('affine_move_y.weight'),
-                     idx('affine_value.weight') if with_value else neg(1, H)]
-        wcat = torch.cat(head_rows + [neg(LDZ - 150, H)], 0)
-        parts16 = {'wt16': wt, 'wtT16': wt.transpose(1, 2).contiguous(), 'wpre16': idx('affine_pre_rnn.weight'),
-                   'bpre16': idx('affine_pre_rnn.bias'), 'wih16': w_in, 'wcat16': wcat,
-                   # (in, 4H) copy for ∂pre = ∂G·W_ih: the ∂X chain's operand K-contiguous per column
-                   'wihT16': w_in.t().contiguous()}
-        if lstm:
-            parts16['whh16'] = idx('rnn.weight_hh_l0')
-        if getattr(fp, 'fp32', False):
-            # (out, in)-transposed pre-RNN weight: the fused ∂X chain's second operand, K-contiguous per column
-            parts16['wpreT'] = idx('affine_pre_rnn.weight').t().contiguous()
-        head_b = [idx('affine_unit_attention.bias'), idx('affine_head_enum.bias'), idx('affine_move_x.bias'),
-                  idx('affine_move_y.bias'), idx('affine_value.bias') if with_value else neg(1)]
-        bcat = torch.cat(head_b + [neg(LDZ - 150)])
-        parts32 = {'bt': (torch.stack([idx(f'affine_unit_{s}.bias') for s in TYPE_SUFFIX]), None),
-                   'bias4': ((idx('rnn.bias_ih_l0')[perm], idx('rnn.bias_hh_l0')[perm]) if lstm
-                             else (idx('fake_rnn.bias'), None)),
-                   'bcat': (bcat, None)}
-        if cfg.entity_attention and getattr(fp, 'fp32', False):
-            # fp32 5v5: the encoder adds b_τ + b_out as well (E0' = E0 + b_out; LayerNorm subtracts it again and the
-            # out-projection then accumulates onto E0' in place: no residual copy, no bias pass)
-            bo = idx('entity_attn.out.bias')
-            parts32['bt'] = (parts32['bt'][0], bo.unsqueeze(0).expand(6, -1))
-            parts32['bout'] = (bo, None)
-        partsS = {}
-        if getattr(fp, 'fp32', False):
-            # fp32 learner: the GEMM operand images are fp32 gathers too (the HIP kernels split them into bf16 hi/lo
-            # pairs themselves)
-            parts32.update({k: (v, None) for k, v in parts16.items()})
-            parts16 = {}
-            # bf16 hi / lo SLAB-MAJOR images [K/32][rows][32] of the chain kernels' weights (ops/csrc/dx_chain.hip):
-            # forward W_pre (256, 896) and W_ih (4H, 256, unit-major rows); ∂X W_ihᵀ (256, 4H) and W_preᵀ (896, 256)
-            def slab(t):
-                return t.reshape(t.shape[0], t.shape[1] // 32, 32).permute(1, 0, 2).contiguous()
-            wpre_i = idx('affine_pre_rnn.weight')
-            wih_i = w_in
-            if getattr(fp, 'exact', False):
-                # IEEE-fp32 learner: the chain kernels take fp32 weights as they are (no hi / lo images); the heads
-                # GEMM's W_cat zero-padded to 256 rows and its transpose (the ∂h product's operand)
-                if H % 128 == 0:
-                    wcat_p = torch.cat([wcat, neg(256 - LDZ, H)], 0)
-                    parts32['wcat256'] = (wcat_p, None)
-                    parts32['wcatT256'] = (wcat_p.t().contiguous(), None)
-                    parts32['bcat256'] = (torch.cat([bcat, neg(256 - LDZ)]), None)
-            elif wpre_i.shape[1] % 128 == 0 and wih_i.shape[0] % 128 == 0:
-                partsS = {'pre_s': slab(wpre_i), 'ih_s': slab(wih_i), 'dx1_s': slab(wih_i.t()),
-                          'dx2_s': slab(wpre_i.t())}
-            if H % 128 == 0 and not getattr(fp, 'exact', False):
-                # heads GEMM and its ∂X product on the chain kernel's stages: W_cat zero-padded to 256 rows
-                wcat_p = torch.cat([wcat, neg(256 - LDZ, H)], 0)
-                partsS['wcat_s'] = slab(wcat_p)
-                partsS['wcatT_s'] = slab(wcat_p.t())
-                parts32['bcat256'] = (torch.cat([bcat, neg(256 - LDZ)]), None)
-            if cfg.entity_attention and getattr(fp, 'exact', False):
-                # the IEEE-fp32 attention block's fp32 weight images, in the fragment orders of its forward (W_qkv,
-                # W_out) and backward (W_outᵀ, W_qkv k16) — gathered here, no per-step split or permute launches
-                wq_i, wo_i = idx('entity_attn.qkv.weight'), idx('entity_attn.out.weight')
-                parts32['wq_x'] = (_frag_order(wq_i), None)
-                parts32['wo_x'] = (_frag_order(wo_i), None)
-                parts32['wot_x'] = (_frag_order(wo_i.t().contiguous()), None)
-                parts32['wq4_x'] = (_k16_order(wq_i), None)
-            elif cfg.entity_attention:
-                # the fused attention block's W_qkv / W_out hi / lo images in MFMA fragment order (attn_block.hip),
-                # from this same gather instead of two split + two permute-copy launches before the block
-                partsS['wq_f'] = _frag_order(idx('entity_attn.qkv.weight'))
-                partsS['wo_f'] = _frag_order(idx('entity_attn.out.weight'))
-                # and the backward's W_outᵀ / W_qkv k16 images
-                partsS['wot_f'] = _frag_order(idx('entity_attn.out.weight').t().contiguous())
-                partsS['wq4_f'] = _k16_order(idx('entity_attn.qkv.weight'))
-        self.shapes16 = {k: tuple(v.shape) for k, v in parts16.items()}
-        self.shapes32 = {k: tuple(v[0].shape) for k, v in parts32.items()}
-        m16 = torch.cat([v.reshape(-1) for v in parts16.values()]) if parts16 else torch.zeros(0, dtype=torch.int64)
-        m32 = torch.cat([torch.stack([a.reshape(-1), (b.reshape(-1) if b is not None else neg(a.numel()))], 1)
-                         for a, b in parts32.values()])
-        # (expand() above is a broadcast view; reshape copies it)
-        self.map16 = m16.to(torch.int32).to(dev)
-        self.map32 = m32.to(torch.int32).contiguous().to(dev)
-        self.buf16 = torch.empty(m16.numel(), dtype=torch.bfloat16, device=dev)
-        self.buf32 = torch.empty(m32.shape[0], dtype=torch.float32, device=dev)
-        self.views: Dict[str, torch.Tensor] = {}
+        # role → (…, 2) source pairs of an fp32 image / → sources of a hi / lo image; the MFMA operands' roles
+        gather, split, operands = {}, {}, set()
+        for role, src, form in _operand_table(cfg, idx, perm, with_value):
+            if form == MAT and any(d % 128 for d in src.shape):
+                raise ValueError(f'WeightImages: {role} is {tuple(src.shape)}; the kernels cover multiples of 128 '
+                                 f'(hidden {cfg.hidden}, pre-RNN width {cfg.pre_rnn_dim})')
+            if form in _ORDER:
+                operands.add(role)
+                src = _ORDER[form][exact](src)
+                if not exact:
+                    split[role] = src
+                    continue
+            a, b = src if form == SUM else (src, torch.full_like(src, -1))
+            gather[role] = torch.stack([a, b], -1)      # (stack copies the broadcast view of a shared second term)
+        self.flat = flat
+        self.map32 = torch.cat([m.reshape(-1, 2) for m in gather.values()]).to(torch.int32).to(dev)
+        self.buf32 = torch.empty(self.map32.shape[0], dtype=torch.float32, device=dev)
         self.mapS = self.bufH = self.bufL = None
-        if partsS:
-            self.mapS = torch.cat([v.reshape(-1) for v in partsS.values()]).to(torch.int32).to(dev)
+        if split:
+            self.mapS = torch.cat([m.reshape(-1) for m in split.values()]).to(torch.int32).to(dev)
             self.bufH = torch.empty(self.mapS.numel(), dtype=torch.bfloat16, device=dev)
             self.bufL = torch.empty_like(self.bufH)
-            o = 0
-            for k, v in partsS.items():
-                self.views[k] = (self.bufH[o:o + v.numel()].view(v.shape), self.bufL[o:o + v.numel()].view(v.shape))
-                o += v.numel()
+        no_lo = torch.empty(0, dtype=torch.float32, device=dev)     # the lo slot of every fp32-exact operand
+        self.views: Dict[str, object] = {}
         o = 0
-        for k, shp in self.shapes16.items():
-            n = 1
-            for d in shp:
-                n *= d
-            self.views[k] = self.buf16[o:o + n].view(shp)
-            o += n
+        for role, m in gather.items():
+            v = self.buf32[o:o + m[..., 0].numel()].view(m.shape[:-1])
+            self.views[role] = (v, no_lo) if role in operands else v
+            o += v.numel()
         o = 0
-        for k, shp in self.shapes32.items():
-            n = 1
-            for d in shp:
-                n *= d
-            self.views[k] = self.buf32[o:o + n].view(shp)
-            o += n
-        self.flat = flat
+        for role, m in split.items():
+            self.views[role] = (self.bufH[o:o + m.numel()].view(m.shape), self.bufL[o:o + m.numel()].view(m.shape))
+            o += m.numel()
 
-    def refresh(self, C) -> Dict[str, torch.Tensor]:
-        if self.mapS is not None:
-            C.weight_prep(self.flat, self.map16, self.buf16, self.map32, self.buf32, self.mapS, self.bufH, self.bufL)
-        else:
-            C.weight_prep(self.flat, self.map16, self.buf16, self.map32, self.buf32)
+    def refresh(self, C) -> Dict[str, object]:
+        C.weight_prep(self.flat, self.map32, self.buf32, self.mapS, self.bufH, self.bufL)
         return self.views
 
 
@@ -242,17 +224,12 @@ class Heads(NamedTuple):
     dxh: torch.Tensor                     # (S, B, H) ∂L/∂h from the heads
 
 
-def _exact_pair(w: torch.Tensor):
-    """An IEEE-fp32 operand in the (hi, lo) argument slots of a kernel that also has a bf16x3 form: (w, empty)."""
-    return w, w.new_empty(0)
-
-
 def _forward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], units_t, env_t, h0, c0, B: int, S: int,
              rst: Optional[torch.Tensor]) -> Forward:
     """Encoder [+ attention block] → forward chain → recurrence (on the side stream) → heads GEMM. On return the
     current stream has joined the side stream."""
     C, cfg = fp.C, fp.cfg
-    exact = bool(getattr(fp, 'exact', False))
+    exact = fp.exact
     lin = cfg.rnn != 'lstm'             # the reference's linear fake_rnn layer (compat preset): no recurrence
     N, U, H = B * S, units_t.shape[1], cfg.hidden
     dev = units_t.device
@@ -261,7 +238,7 @@ def _forward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], units_t
     w1, b1 = P['affine_unit_basic_stats.weight'].detach(), P['affine_unit_basic_stats.bias'].detach()
     we, be = P['affine_env.weight'].detach(), P['affine_env.bias'].detach()
     # (exact: the IEEE-fp32 encoder variant, ops/csrc/encoder.hip encoder_fwd_x_kernel)
-    x896, emb, arg = C.encoder_fwd(units_t, env_t, w1, b1, W['wt16'], W['bt'], we, be, list(cfg.layout.counts),
+    x896, emb, arg = C.encoder_fwd(units_t, env_t, w1, b1, W['enc_w'], W['enc_b'], we, be, list(cfg.layout.counts),
                                    bool(cfg.compat_bugs), exact=exact)
     attn = None
     if cfg.entity_attention:
@@ -270,11 +247,10 @@ def _forward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], units_t
         # bt) → pools / argmax of the attended embeddings; bf16x3 operands (hi / lo fragment images), or the IEEE-fp32
         # twin on fp32 fragment images at fp32-exact. E0' stays untouched (the LayerNorm backward's input), E1 is new
         E0p = emb.view(N * U, 128)
-        wq, wo = (_exact_pair(W['wq_x']), _exact_pair(W['wo_x'])) if exact else (W['wq_f'], W['wo_f'])
         arg = torch.empty(N, 6, 128, dtype=torch.uint8, device=dev)
         Xn, ln_mu, ln_rs, QKV, Oat, lse, E1 = C.attn_block_fwd(
-            E0p, W['bout'], P['entity_attn.ln.weight'].detach(), P['entity_attn.ln.bias'].detach(), wq[0], wq[1],
-            P['entity_attn.qkv.bias'].detach(), wo[0], wo[1], fp.type_offset_list(), x896, arg,
+            E0p, W['attn_out_b'], P['entity_attn.ln.weight'].detach(), P['entity_attn.ln.bias'].detach(),
+            *W['attn_qkv_w'], P['entity_attn.qkv.bias'].detach(), *W['attn_out_w'], fp.type_offset_list(), x896, arg,
             bool(cfg.compat_bugs), 1e-5)
         emb = E1.view(N, U, 128)
         attn = (E0p, Xn, ln_mu, ln_rs, QKV, Oat, lse)
@@ -283,11 +259,10 @@ def _forward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], units_t
         arg[:, 5] = arg[:, 3]
     # the forward chain relu(x896·W_preᵀ + b)·W_ihᵀ in ONE kernel (ops/csrc/dx_chain.hip; x16 > 0 ⟺ x > 0): slab-major
     # bf16 hi / lo weight images, or the fp32 weights as they are on v_mfma_f32_16x16x4_f32
-    fw1, fw2 = (_exact_pair(W['wpre16']), _exact_pair(W['wih16'])) if exact else (W['pre_s'], W['ih_s'])
-    x16, xp = C.pre_rnn_chain(x896, fw1[0], fw1[1], W['bpre16'], fw2[0], fw2[1])
+    x16, xp = C.pre_rnn_chain(x896, *W['pre_w'], W['pre_b'], *W['in_w'])
     if lin:
         # fake_rnn: h = pre·W_fᵀ + b_f (the chain kernel's second product) — no activation, no recurrence
-        hs = xp.add_(W['bias4']).view(S, B, H)
+        hs = xp.add_(W['rec_b']).view(S, B, H)
         cs = gates4 = None
     else:
         hs = torch.empty(S, B, H, device=dev)
@@ -296,12 +271,11 @@ def _forward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], units_t
     sL.wait_stream(main)
     if not lin:
         with torch.cuda.stream(sL):
-            team_fwd(C, xp.view(S, B, H, 4), W['whh16'], h0, c0, fp.err, False, time_major=True, hs_out=hs,
-                     cs_out=cs, gates_out=gates4, bias4=W['bias4'], reset=rst)
+            team_fwd(C, xp.view(S, B, H, 4), W['rec_w'], h0, c0, fp.err, False, time_major=True, hs_out=hs,
+                     cs_out=cs, gates_out=gates4, bias4=W['rec_b'], reset=rst)
         main.wait_stream(sL)
     # heads GEMM on the chain kernel's stages (bf16x3 images, or exact: fp32 W_cat padded to 256 rows)
-    wc = _exact_pair(W['wcat256']) if exact else W['wcat_s']
-    z = C.rowmm_out256(hs.view(N, H), wc[0], wc[1], W['bcat256'])   # (N, 256), padding columns 0
+    z = C.rowmm_out256(hs.view(N, H), *W['heads_w'], W['heads_b'])   # (N, 256), padding columns 0
     return Forward(x896, emb, arg, x16, hs, cs, gates4, z, attn)
 
 
@@ -310,7 +284,7 @@ def _heads_loss(fp, W: Dict[str, torch.Tensor], f: Forward, act_t, msk_t, adv_t,
     """The heads / loss kernel (loss partials, log-probs, ∂z, ∂pointer logits) and ∂h = ∂z·W_cat, preceded by the
     in-step V-trace when ``vt_t`` is given. Sets ``fp.vtrace_stats``."""
     C, lc = fp.C, fp.loss_cfg
-    exact = bool(getattr(fp, 'exact', False))
+    exact = fp.exact
     N, H = B * S, fp.cfg.hidden
     # heads_loss algo: 0 = PPO clipped surrogate, 1 = VPG (reference), 2 = PPO's truncated-IS off-policy term
     algo = (2 if getattr(lc, 'offpolicy', 'clip') == 'tis' else 0) if lc.algo == 'ppo' else 1
@@ -339,8 +313,7 @@ def _heads_loss(fp, W: Dict[str, torch.Tensor], f: Forward, act_t, msk_t, adv_t,
     dz, dtl, part, logp = C.heads_loss(f.z, f.emb, act_t, msk_t, adv_t, ret_t, lpo_t, nret_t, norms, algo,
                                        bool(lc.compat_value_bug), S, B, float(lc.clip_eps), float(lc.entropy_coef),
                                        float(lc.vf_coef), dz_bf16=False, precise=exact)
-    wct = _exact_pair(W['wcatT256']) if exact else W['wcatT_s']
-    dxh = C.rowmm_in256(dz, wct[0], wct[1]).view(S, B, H)
+    dxh = C.rowmm_in256(dz, *W['heads_wT']).view(S, B, H)
     return Heads(part, logp, dz, dtl, dxh)
 
 
@@ -353,7 +326,7 @@ def _backward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], f: For
     returning. ``heads_done``: recorded on the main stream after :func:`_heads_loss`."""
     from ..ops.gemm import gemm_tn as _gemm_tn
     C, cfg = fp.C, fp.cfg
-    exact = bool(getattr(fp, 'exact', False))
+    exact = fp.exact
     lin = cfg.rnn != 'lstm'
     attn = cfg.entity_attention
     N, H = B * S, cfg.hidden
@@ -363,7 +336,6 @@ def _backward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], f: For
     counts = list(cfg.layout.counts)
     w1, b1 = P['affine_unit_basic_stats.weight'].detach(), P['affine_unit_basic_stats.bias'].detach()
     we, be = P['affine_env.weight'].detach(), P['affine_env.bias'].detach()
-    wpre = W['wpre16']
 
     def gemm_tn(*a, **k):
         # weight gradients: split-K MFMA over the B·S rows (ops/csrc/gemm_tn.hip), written in PyTorch's gate-major row
@@ -390,13 +362,13 @@ def _backward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], f: For
     else:
         dWhh = gout['rnn.weight_hh_l0'] if direct else torch.zeros(4 * H, H, device=dev)
         dWih = gout['rnn.weight_ih_l0'] if direct else torch.zeros(4 * H, f.x16.shape[1], device=dev)
-    dWpre = gout['affine_pre_rnn.weight'] if direct else torch.zeros(wpre.shape[0], wpre.shape[1], device=dev)
-    dbpre = gout['affine_pre_rnn.bias'] if direct else torch.zeros(wpre.shape[0], device=dev)
+    dWpre = gout['affine_pre_rnn.weight'] if direct else torch.zeros_like(P['affine_pre_rnn.weight'])
+    dbpre = gout['affine_pre_rnn.bias'] if direct else torch.zeros_like(P['affine_pre_rnn.bias'])
     sL.wait_event(heads_done)
     db = None
     with torch.cuda.stream(sL):
         if not lin:
-            db = team_bwd(C, hd.dxh, f.gates4, f.cs, c0, None, None, W['whh16'], fp.err, time_major=True,
+            db = team_bwd(C, hd.dxh, f.gates4, f.cs, c0, None, None, W['rec_w'], fp.err, time_major=True,
                           dg_out=dgates, dg_bf16=False, want_dbias=True, reset=rst)[3]
             bwd_done = torch.cuda.Event()
             bwd_done.record(sL)
@@ -418,8 +390,7 @@ def _backward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], f: For
             gemm_tn(dG, f.x16, out=dWih, perm=gperm, accumulate=True)
     # ∂pre = (∂G·W_ih)⊙[x16 > 0] and ∂x896 = ∂pre·W_pre in one launch (the ∂pre tile stays in LDS); operands: bf16
     # hi / lo slab images, or the fp32 transposes as they are
-    dx1, dx2 = (_exact_pair(W['wihT16']), _exact_pair(W['wpreT'])) if exact else (W['dx1_s'], W['dx2_s'])
-    dpre, dx896 = C.dpre_dx(dG, dx1[0], dx1[1], f.x16, dx2[0], dx2[1])
+    dpre, dx896 = C.dpre_dx(dG, *W['dx_in_wT'], f.x16, *W['dx_pre_wT'])
 
     def wpre_grad():
         gemm_tn(dpre, f.x896, out=dWpre, accumulate=True, colsum=dbpre)
@@ -446,11 +417,10 @@ def _backward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], f: For
     if attn:
         # one kernel from ∂x896 / the pointer gradient to ∂E0
         E0p, Xn, ln_mu, ln_rs, QKV, Oat, lse = f.attn
-        wot, wq4 = (_exact_pair(W['wot_x']), _exact_pair(W['wq4_x'])) if exact else (W['wot_f'], W['wq4_f'])
         dE1, dQKV, demb_in, lnsum = C.attn_block_bwd(
             hd.dtl, f.z, dx896, f.arg, fp.type_offset_list(), bool(cfg.compat_bugs), Oat, QKV,
-            P['entity_attn.qkv.bias'].detach(), lse, E0p, W['bout'], ln_mu, ln_rs,
-            P['entity_attn.ln.weight'].detach(), wot[0], wot[1], wq4[0], wq4[1], None)
+            P['entity_attn.qkv.bias'].detach(), lse, E0p, W['attn_out_b'], ln_mu, ln_rs,
+            P['entity_attn.ln.weight'].detach(), *W['attn_out_wT'], *W['attn_qkv_k16'], None)
 
     def side_tail():
         with torch.cuda.stream(sL):
@@ -466,7 +436,7 @@ def _backward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], f: For
     sL.wait_stream(main)
     if not attn:
         dbt, dWe, dbe = side_tail()
-    dWt, dw1, db1 = C.encoder_bwd(units_t, w1, b1, W['wtT16'], hd.dtl, f.z, dx896, f.arg, counts,
+    dWt, dw1, db1 = C.encoder_bwd(units_t, w1, b1, W['enc_wT'], hd.dtl, f.z, dx896, f.arg, counts,
                                   bool(cfg.compat_bugs), demb_in=demb_in, exact=exact)
     if pre_main:
         wpre_grad()
@@ -509,12 +479,12 @@ def fused_step_tm(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], un
     """Loss partials and all parameter gradients of one minibatch, from TIME-MAJOR rows (row = t·B + b): forward →
     heads / loss → backward, every product on a hand-written kernel (no torch GEMM, so no matmul mode to pin).
 
-    ``W`` = :class:`WeightImages` views, ``P`` = fp32 parameters (for the small fp32 weights used directly).
+    ``W`` = :class:`WeightImages` operands by role, ``P`` = fp32 parameters (the small fp32 weights used directly).
     ``gout`` (direct mode): parameter name → gradient tensor (a view of the flat gradient buffer); the big
     weight-gradient GEMMs (W_hh, W_ih, pre-RNN) ACCUMULATE straight into those and are left out of ``grads``.
     Returns (partials (R,16) f32, logp (N) f32 time-major, grads {param name → tensor})."""
-    assert getattr(fp, 'fp32', False), 'the fused step runs at fp32 / fp32-exact (bf16: torch backend)'
-    if getattr(fp, 'exact', False) and B > 32 and fp.cfg.rnn == 'lstm':
+    assert fp.fp32, 'the fused step runs at fp32 / fp32-exact (bf16: torch backend)'
+    if fp.exact and B > 32 and fp.cfg.rnn == 'lstm':
         # lstm_team.hip plan(): the sequences run as chains of ≤ 4 rows (one XCD team each) on the exact fp32 VALU
         # recurrence; more than 4 rows per chain take the bf16x3 MFMA team kernel — not IEEE fp32
         raise ValueError(f'fp32-exact: at most 32 sequences per step and GPU (got {B}); use precision fp32')
@@ -624,5 +594,5 @@ def forward_logp_value(fp, units_t, env_t, act_t, msk_t, h0, c0, B: int, S: int,
     norms = fp.scratch('fwd_norms', (8,), torch.float32, dev)
     # the heads kernel's selected-action log-prob (its loss partials / gradients are not used here)
     _, _, _, lp = C.heads_loss(f.z, f.emb, act_t, msk_t, zero, zero, zero, zero, norms, 0, False, S, B, 0.1, 0.0, 0.0,
-                               dz_bf16=False, precise=bool(getattr(fp, 'exact', False)))
+                               dz_bf16=False, precise=fp.exact)
     return lp, f.z[:, 149].contiguous()

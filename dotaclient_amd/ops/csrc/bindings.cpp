@@ -31,6 +31,47 @@ inline void hip_check(hipError_t e, const char* what) {
 template <typename T>
 inline T* ptr(const torch::Tensor& t) { return reinterpret_cast<T*>(t.data_ptr()); }
 
+// One MFMA weight operand in its (hi, lo) argument slots (models/pipelined.py WeightImages): a bf16 hi / lo image pair
+// of one shape (bf16x3, x = hi + lo), or the fp32 image with an empty lo (IEEE fp32, `exact`). `numel` >= 0: the
+// expected element count of the image.
+struct Operand {
+  const void* hi;
+  const void* lo;      // nullptr when exact
+  bool exact;
+};
+inline Operand operand(const torch::Tensor& hi, const torch::Tensor& lo, int64_t numel, const char* name) {
+  TORCH_CHECK(hi.is_cuda() && hi.is_contiguous(), name, " must be a contiguous GPU tensor");
+  TORCH_CHECK(numel < 0 || hi.numel() == numel, name, " must hold ", numel, " elements");
+  if (hi.scalar_type() == at::kFloat) {
+    TORCH_CHECK(lo.numel() == 0, name, ": an fp32 (exact) image takes an empty lo image");
+    return {hi.data_ptr(), nullptr, true};
+  }
+  TORCH_CHECK(hi.scalar_type() == at::kBFloat16, name, " must be fp32 (exact) or a bf16 hi / lo pair");
+  TORCH_CHECK(lo.is_cuda() && lo.is_contiguous() && lo.scalar_type() == at::kBFloat16 && lo.sizes() == hi.sizes(),
+              name, ": the lo image must be a contiguous bf16 GPU tensor of the hi image's shape");
+  return {hi.data_ptr(), lo.data_ptr(), false};
+}
+// All operands of one call at one precision; returns it.
+inline bool same_precision(std::initializer_list<Operand> ops, const char* who) {
+  const bool exact = ops.begin()->exact;
+  for (const Operand& o : ops)
+    TORCH_CHECK(o.exact == exact, who, ": all weights fp32 (exact) or all bf16 hi / lo pairs");
+  return exact;
+}
+// A chain-kernel weight W (rows, K) (dx_chain.hip): slab-major hi / lo images (K/32, rows, 32), or the fp32 matrix.
+struct ChainOperand : Operand {
+  int64_t rows, K;
+};
+inline ChainOperand chain_operand(const torch::Tensor& hi, const torch::Tensor& lo, const char* name) {
+  const Operand o = operand(hi, lo, -1, name);
+  if (o.exact) {
+    TORCH_CHECK(hi.dim() == 2, name, ": an exact weight is a 2-D fp32 matrix (rows, K)");
+    return {o, hi.size(0), hi.size(1)};
+  }
+  TORCH_CHECK(hi.dim() == 3 && hi.size(2) == 32, name, ": bf16x3 weights are slab-major images (K/32, rows, 32)");
+  return {o, hi.size(1), hi.size(0) * 32};
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // header: leading elements of the flat buffers that are not parameters (excluded from the norm); skip: optional
 // 1-element f32 device flag — nonzero → the step changes nothing (failed recurrence on some DP rank).
@@ -612,19 +653,14 @@ std::vector<torch::Tensor> attn_block_fwd(torch::Tensor e0, torch::Tensor bout, 
                                           torch::Tensor wol, std::vector<int64_t> type_off, torch::Tensor x896,
                                           torch::Tensor arg, bool compat, double eps) {
   CHECK_F32(e0); CHECK_F32(bout); CHECK_F32(gamma); CHECK_F32(beta); CHECK_F32(bq); CHECK_F32(x896); CHECK_U8(arg);
-  // fp32 weight images (wql / wol ignored): the IEEE-fp32 kernel; bf16 hi / lo images: bf16x3
-  const bool exact = wqh.scalar_type() == at::kFloat;
-  CHECK_DEV(wqh); CHECK_CONTIG(wqh); CHECK_DEV(woh); CHECK_CONTIG(woh);
-  if (exact) {
-    CHECK_F32(woh);
-  } else {
-    CHECK_BF16(wqh); CHECK_BF16(wql); CHECK_BF16(woh); CHECK_BF16(wol);
-  }
+  // fp32 weight images: the IEEE-fp32 kernel; bf16 hi / lo images: bf16x3
+  const Operand wq = operand(wqh, wql, 384 * 128, "attn_block_fwd: W_qkv"),
+                wo = operand(woh, wol, 128 * 128, "attn_block_fwd: W_out");
+  const bool exact = same_precision({wq, wo}, "attn_block_fwd");
   TORCH_CHECK(e0.numel() % (64 * 128) == 0 && e0.size(-1) == 128, "attn_block_fwd: e0 (N·64, 128)");
   const int64_t N = e0.numel() / (64 * 128);
-  TORCH_CHECK(wqh.numel() == 384 * 128 && (exact || wql.numel() == 384 * 128) && woh.numel() == 128 * 128 &&
-              (exact || wol.numel() == 128 * 128) && bq.numel() == 384 && bout.numel() == 128 && gamma.numel() == 128 &&
-              beta.numel() == 128, "attn_block_fwd: weight shapes");
+  TORCH_CHECK(bq.numel() == 384 && bout.numel() == 128 && gamma.numel() == 128 && beta.numel() == 128,
+              "attn_block_fwd: weight shapes");
   TORCH_CHECK(x896.dim() == 2 && x896.size(0) == N && x896.size(1) == 896, "attn_block_fwd: x896 (N, 896)");
   TORCH_CHECK(arg.numel() == N * 6 * 128, "attn_block_fwd: arg (N, 6, 128)");
   TORCH_CHECK(type_off.size() == 7 && type_off[0] == 0 && type_off[6] == 64, "attn_block_fwd: 7 type offsets 0 … 64");
@@ -639,11 +675,10 @@ std::vector<torch::Tensor> attn_block_fwd(torch::Tensor e0, torch::Tensor bout, 
   auto lse = torch::empty({N, 4, 64}, o32);
   auto e1 = torch::empty({N * 64, 128}, o32);
   hip_check(dca_attn_block_fwd_f32(ptr<float>(e0), ptr<float>(bout), ptr<float>(gamma), ptr<float>(beta),
-                                   wqh.data_ptr(), exact ? nullptr : wql.data_ptr(), ptr<float>(bq), woh.data_ptr(),
-                                   exact ? nullptr : wol.data_ptr(), ptr<float>(xn), ptr<float>(mu), ptr<float>(rs),
-                                   ptr<float>(qkv), ptr<float>(o), ptr<float>(lse), ptr<float>(e1), ptr<float>(x896),
-                                   ptr<unsigned char>(arg), off, compat ? 1 : 0, (int)N, (float)eps, cur_stream(),
-                                   exact ? 1 : 0),
+                                   wq.hi, wq.lo, ptr<float>(bq), wo.hi, wo.lo, ptr<float>(xn), ptr<float>(mu),
+                                   ptr<float>(rs), ptr<float>(qkv), ptr<float>(o), ptr<float>(lse), ptr<float>(e1),
+                                   ptr<float>(x896), ptr<unsigned char>(arg), off, compat ? 1 : 0, (int)N, (float)eps,
+                                   cur_stream(), exact ? 1 : 0),
             "dca_attn_block_fwd_f32");
   return {xn, mu, rs, qkv, o, lse, e1};
 }
@@ -665,13 +700,10 @@ std::vector<torch::Tensor> attn_block_bwd(torch::Tensor dtl, torch::Tensor q, to
                                           torch::Tensor wq4l, c10::optional<torch::Tensor> trace) {
   CHECK_F32(dtl); CHECK_DEV(q); CHECK_DT(q, at::kFloat); CHECK_F32(dx); CHECK_U8(arg); CHECK_F32(o); CHECK_F32(qkv);
   CHECK_F32(bq); CHECK_F32(lse); CHECK_F32(e0); CHECK_F32(bout); CHECK_F32(mu); CHECK_F32(rs); CHECK_F32(gamma);
-  const bool exact = woth.scalar_type() == at::kFloat;     // fp32 images: the IEEE-fp32 kernel
-  CHECK_DEV(woth); CHECK_CONTIG(woth); CHECK_DEV(wq4h); CHECK_CONTIG(wq4h);
-  if (exact) {
-    CHECK_F32(wq4h);
-  } else {
-    CHECK_BF16(woth); CHECK_BF16(wotl); CHECK_BF16(wq4h); CHECK_BF16(wq4l);
-  }
+  // fp32 images: the IEEE-fp32 kernel
+  const Operand wot = operand(woth, wotl, 128 * 128, "attn_block_bwd: W_out^T"),
+                wq4 = operand(wq4h, wq4l, 384 * 128, "attn_block_bwd: W_qkv k16");
+  const bool exact = same_precision({wot, wq4}, "attn_block_bwd");
   check_type_off(type_off);
   const int64_t N = dtl.size(0);
   TORCH_CHECK(dtl.dim() == 2 && dtl.size(1) == 64, "attn_block_bwd: dtl (N, 64)");
@@ -680,9 +712,7 @@ std::vector<torch::Tensor> attn_block_bwd(torch::Tensor dtl, torch::Tensor q, to
   TORCH_CHECK(arg.numel() == N * 6 * 128, "attn_block_bwd: arg (N, 6, 128)");
   TORCH_CHECK(o.numel() == N * 64 * 128 && e0.numel() == N * 64 * 128 && qkv.numel() == N * 64 * 384 &&
               lse.numel() == N * 4 * 64 && mu.numel() == N * 64 && rs.numel() == N * 64, "attn_block_bwd: saved shapes");
-  TORCH_CHECK(bq.numel() == 384 && bout.numel() == 128 && gamma.numel() == 128 && woth.numel() == 128 * 128 &&
-              (exact || wotl.numel() == 128 * 128) && wq4h.numel() == 384 * 128 &&
-              (exact || wq4l.numel() == 384 * 128), "attn_block_bwd: weight shapes");
+  TORCH_CHECK(bq.numel() == 384 && bout.numel() == 128 && gamma.numel() == 128, "attn_block_bwd: weight shapes");
   int off[7];
   for (int i = 0; i < 7; ++i) off[i] = (int)type_off[i];
   auto o32 = e0.options();
@@ -701,9 +731,8 @@ std::vector<torch::Tensor> attn_block_bwd(torch::Tensor dtl, torch::Tensor q, to
   hip_check(dca_attn_block_bwd_f32(ptr<float>(dtl), ptr<float>(q), (int)q.stride(0), ptr<float>(dx),
                                    ptr<unsigned char>(arg), off, compat ? 1 : 0, ptr<float>(o), ptr<float>(qkv),
                                    ptr<float>(bq), ptr<float>(lse), ptr<float>(e0), ptr<float>(bout), ptr<float>(mu),
-                                   ptr<float>(rs), ptr<float>(gamma), woth.data_ptr(),
-                                   exact ? nullptr : wotl.data_ptr(), wq4h.data_ptr(),
-                                   exact ? nullptr : wq4l.data_ptr(), ptr<float>(de1), ptr<float>(dqkv),
+                                   ptr<float>(rs), ptr<float>(gamma), wot.hi, wot.lo, wq4.hi, wq4.lo,
+                                   ptr<float>(de1), ptr<float>(dqkv),
                                    ptr<float>(de0), ptr<float>(part), ptr<float>(tmp), ptr<float>(sums), (int)N,
                                    cur_stream(),
                                    (trace.has_value() && trace->defined()) ? ptr<unsigned long long>(*trace) : nullptr,
@@ -878,13 +907,12 @@ void loss_assemble(torch::Tensor part, torch::Tensor norms, int64_t N, int64_t a
             "dca_loss_assemble");
 }
 
-// Working copies of the weights: dst16[i] = bf16(src[map16[i]]) (0 where map16 < 0),
-// dst32[i] = src[map32[i,0]] + src[map32[i,1]] (negative index = 0 term).
-void weight_prep(torch::Tensor src, torch::Tensor map16, torch::Tensor dst16, torch::Tensor map32,
-                 torch::Tensor dst32, c10::optional<torch::Tensor> maps, c10::optional<torch::Tensor> dsth,
-                 c10::optional<torch::Tensor> dstl) {
-  CHECK_F32(src); CHECK_I32(map16); CHECK_BF16(dst16); CHECK_I32(map32); CHECK_F32(dst32);
-  TORCH_CHECK(map16.numel() == dst16.numel() && map32.numel() == 2 * dst32.numel(), "weight_prep: map sizes");
+// Working copies of the weights: dst32[i] = src[map32[i,0]] + src[map32[i,1]] (negative index = 0 term); optional bf16
+// hi / lo split images dsth[i] + dstl[i] = src[maps[i]] (0 where maps < 0).
+void weight_prep(torch::Tensor src, torch::Tensor map32, torch::Tensor dst32, c10::optional<torch::Tensor> maps,
+                 c10::optional<torch::Tensor> dsth, c10::optional<torch::Tensor> dstl) {
+  CHECK_F32(src); CHECK_I32(map32); CHECK_F32(dst32);
+  TORCH_CHECK(map32.numel() == 2 * dst32.numel(), "weight_prep: map sizes");
   const int* ms = nullptr;
   short *dh = nullptr, *dl = nullptr;
   int ns = 0;
@@ -894,8 +922,8 @@ void weight_prep(torch::Tensor src, torch::Tensor map16, torch::Tensor dst16, to
     TORCH_CHECK(maps->numel() == dsth->numel() && dstl->numel() == dsth->numel(), "weight_prep: split map sizes");
     ms = ptr<int>(*maps); dh = ptr<short>(*dsth); dl = ptr<short>(*dstl); ns = (int)maps->numel();
   }
-  hip_check(dca_weight_prep(ptr<float>(src), ptr<int>(map16), ptr<short>(dst16), (int)dst16.numel(), ptr<int>(map32),
-                            ptr<float>(dst32), (int)dst32.numel(), ms, dh, dl, ns, cur_stream()),
+  hip_check(dca_weight_prep(ptr<float>(src), ptr<int>(map32), ptr<float>(dst32), (int)dst32.numel(), ms, dh, dl, ns,
+                            cur_stream()),
             "dca_weight_prep");
 }
 
@@ -1008,38 +1036,20 @@ std::vector<torch::Tensor> split_bf16x2(torch::Tensor src, bool slab_major) {
 // Returns (dpre (N, 256), dx (N, X)).
 std::vector<torch::Tensor> dpre_dx(torch::Tensor dG, torch::Tensor w1h, torch::Tensor w1l, torch::Tensor x,
                                    torch::Tensor w2h, torch::Tensor w2l) {
-  CHECK_F32(dG); CHECK_F32(x); CHECK_DEV(w1h); CHECK_CONTIG(w1h); CHECK_DEV(w2h); CHECK_CONTIG(w2h);
-  const bool exact = w1h.scalar_type() == at::kFloat;
-  if (exact) {
-    TORCH_CHECK(w2h.scalar_type() == at::kFloat, "dpre_dx: both weights fp32 (exact) or bf16 hi/lo pairs");
-  } else {
-    CHECK_DT(w1h, at::kBFloat16); CHECK_DT(w2h, at::kBFloat16); CHECK_DEV(w1l); CHECK_CONTIG(w1l);
-    CHECK_DEV(w2l); CHECK_CONTIG(w2l); CHECK_DT(w1l, at::kBFloat16); CHECK_DT(w2l, at::kBFloat16);
-    TORCH_CHECK(w1l.sizes() == w1h.sizes() && w2l.sizes() == w2h.sizes(), "dpre_dx: hi / lo image shapes");
-  }
-  const int N = dG.size(0), K1 = dG.size(1);
+  CHECK_F32(dG); CHECK_F32(x);
+  const ChainOperand w1 = chain_operand(w1h, w1l, "dpre_dx: W_ih^T"), w2 = chain_operand(w2h, w2l, "dpre_dx: W_pre^T");
+  const bool exact = same_precision({w1, w2}, "dpre_dx");
   TORCH_CHECK(dG.dim() == 2 && x.dim() == 2, "dpre_dx: 2-D dG and x");
-  int X;
-  if (exact) {
-    TORCH_CHECK(w1h.dim() == 2 && w2h.dim() == 2, "dpre_dx: exact weights (256,K1) (X,256)");
-    X = w2h.size(0);
-    TORCH_CHECK(w1h.size(0) == 256 && w1h.size(1) == K1 && w2h.size(1) == 256, "dpre_dx: shapes (256,K1) (X,256)");
-  } else {
-    // slab-major images (split_bf16x2(..., slab_major=True)): (K1/32, 256, 32) and (256/32, X, 32)
-    TORCH_CHECK(w1h.dim() == 3 && w2h.dim() == 3 && w1h.size(0) * 32 == K1 && w1h.size(1) == 256 &&
-                w1h.size(2) == 32 && w2h.size(0) == 8 && w2h.size(2) == 32,
-                "dpre_dx: bf16x3 weights are slab-major images (K1/32,256,32) and (8,X,32)");
-    X = w2h.size(1);
-  }
+  const int N = dG.size(0), K1 = dG.size(1), X = (int)w2.rows;
+  TORCH_CHECK(w1.rows == 256 && w1.K == K1 && w2.K == 256, "dpre_dx: weights (256, K1) and (X, 256)");
   TORCH_CHECK(x.size(0) == N && x.size(1) == 256, "dpre_dx: x (N,256)");
   TORCH_CHECK(K1 % 128 == 0 && X % 128 == 0, "dpre_dx: K1 % 128 == 0 and X % 128 == 0");
   TORCH_CHECK((long long)N * K1 * 4 <= 0x7fff0000LL, "dpre_dx: dG too large for one launch");
   auto o = dG.options();
   auto dpre = torch::empty({N, 256}, o);
   auto dx = torch::empty({N, X}, o);
-  hip_check(dca_dpre_dx(ptr<float>(dG), w1h.data_ptr(), exact ? nullptr : w1l.data_ptr(), ptr<float>(x),
-                        w2h.data_ptr(), exact ? nullptr : w2l.data_ptr(), ptr<float>(dpre), ptr<float>(dx), N, K1, X,
-                        exact ? 1 : 0, 0, cur_stream()),
+  hip_check(dca_dpre_dx(ptr<float>(dG), w1.hi, w1.lo, ptr<float>(x), w2.hi, w2.lo, ptr<float>(dpre), ptr<float>(dx), N,
+                        K1, X, exact ? 1 : 0, 0, cur_stream()),
             "dca_dpre_dx");
   return {dpre, dx};
 }
@@ -1049,53 +1059,30 @@ std::vector<torch::Tensor> dpre_dx(torch::Tensor dG, torch::Tensor w1h, torch::T
 // rowmm_out256: C (N, 256) = A (N, K) · Wᵀ + b with W (256, K) → images (K/32, 256, 32) — stage 1, bias epilogue;
 // rowmm_in256:  C (N, X) = A (N, 256) · Wᵀ with W (X, 256) → images (8, X, 32) — stage 2 on A read from HBM.
 // The 1v1 heads GEMM (W_cat zero-padded to 256 rows) and its ∂X product.
-static bool chain_exact(const torch::Tensor& wh, const torch::Tensor& wl, const char* what) {
-  CHECK_DEV(wh); CHECK_CONTIG(wh);
-  if (wh.scalar_type() == at::kFloat) {
-    TORCH_CHECK(wh.dim() == 2 && wl.numel() == 0, what, ": exact weights are 2-D fp32 with an empty lo image");
-    return true;
-  }
-  CHECK_BF16(wh); CHECK_BF16(wl);
-  TORCH_CHECK(wl.sizes() == wh.sizes(), what, ": hi / lo image shapes");
-  return false;
-}
-
 torch::Tensor rowmm_out256(torch::Tensor A, torch::Tensor wh, torch::Tensor wl, torch::Tensor bias) {
   CHECK_F32(A); CHECK_F32(bias);
-  const bool exact = chain_exact(wh, wl, "rowmm_out256");
+  const ChainOperand w = chain_operand(wh, wl, "rowmm_out256: W");
+  TORCH_CHECK(A.dim() == 2, "rowmm_out256: A (N, K)");
   const int N = A.size(0), K = A.size(1);
-  TORCH_CHECK(A.dim() == 2 && K % 128 == 0 && bias.numel() == 256, "rowmm_out256: A (N, K % 128 == 0), bias (256)");
-  if (exact) {
-    TORCH_CHECK(wh.size(0) == 256 && wh.size(1) == K, "rowmm_out256: exact W (256, K)");
-  } else {
-    TORCH_CHECK(wh.dim() == 3 && wh.size(0) * 32 == K && wh.size(1) == 256 && wh.size(2) == 32,
-                "rowmm_out256: slab-major images (K/32, 256, 32)");
-  }
+  TORCH_CHECK(K % 128 == 0 && bias.numel() == 256, "rowmm_out256: A (N, K % 128 == 0), bias (256)");
+  TORCH_CHECK(w.rows == 256 && w.K == K, "rowmm_out256: W (256, K)");
   TORCH_CHECK((long long)N * K * 4 <= 0x7fff0000LL, "rowmm_out256: A too large for one launch");
   auto out = torch::empty({N, 256}, A.options());
-  hip_check(dca_dpre_dx(ptr<float>(A), wh.data_ptr(), exact ? nullptr : wl.data_ptr(), ptr<float>(bias), nullptr,
-                        nullptr, ptr<float>(out), nullptr, N, K, 0, exact ? 1 : 0, 2, cur_stream()),
+  hip_check(dca_dpre_dx(ptr<float>(A), w.hi, w.lo, ptr<float>(bias), nullptr, nullptr, ptr<float>(out), nullptr, N, K, 0,
+                        w.exact ? 1 : 0, 2, cur_stream()),
             "dca_dpre_dx(stage 1)");
   return out;
 }
 
 torch::Tensor rowmm_in256(torch::Tensor A, torch::Tensor wh, torch::Tensor wl) {
   CHECK_F32(A);
-  const bool exact = chain_exact(wh, wl, "rowmm_in256");
-  const int N = A.size(0);
+  const ChainOperand w = chain_operand(wh, wl, "rowmm_in256: W");
   TORCH_CHECK(A.dim() == 2 && A.size(1) == 256, "rowmm_in256: A (N, 256)");
-  int X;
-  if (exact) {
-    TORCH_CHECK(wh.size(1) == 256 && wh.size(0) % 128 == 0, "rowmm_in256: exact W (X, 256), X % 128 == 0");
-    X = wh.size(0);
-  } else {
-    TORCH_CHECK(wh.dim() == 3 && wh.size(0) == 8 && wh.size(2) == 32 && wh.size(1) % 128 == 0,
-                "rowmm_in256: slab-major images (8, X, 32), X % 128 == 0");
-    X = wh.size(1);
-  }
+  const int N = A.size(0), X = (int)w.rows;
+  TORCH_CHECK(w.K == 256 && X % 128 == 0, "rowmm_in256: W (X, 256), X % 128 == 0");
   auto out = torch::empty({N, X}, A.options());
-  hip_check(dca_dpre_dx(ptr<float>(A), nullptr, nullptr, nullptr, wh.data_ptr(), exact ? nullptr : wl.data_ptr(),
-                        nullptr, ptr<float>(out), N, 0, X, exact ? 1 : 0, 0, cur_stream()),
+  hip_check(dca_dpre_dx(ptr<float>(A), nullptr, nullptr, nullptr, w.hi, w.lo, nullptr, ptr<float>(out), N, 0, X,
+                        w.exact ? 1 : 0, 0, cur_stream()),
             "dca_dpre_dx(stage 2)");
   return out;
 }
@@ -1107,29 +1094,19 @@ std::vector<torch::Tensor> pre_rnn_chain(torch::Tensor x896, torch::Tensor w1h, 
                                          torch::Tensor w2h, torch::Tensor w2l, c10::optional<torch::Tensor> x_out,
                                          c10::optional<torch::Tensor> xp_out) {
   CHECK_F32(x896); CHECK_F32(bias);
-  const bool exact = chain_exact(w1h, w1l, "pre_rnn_chain");
-  TORCH_CHECK(chain_exact(w2h, w2l, "pre_rnn_chain") == exact, "pre_rnn_chain: both weights exact or both bf16x3");
-  const int N = x896.size(0), K1 = x896.size(1);
+  const ChainOperand w1 = chain_operand(w1h, w1l, "pre_rnn_chain: W_pre"),
+                     w2 = chain_operand(w2h, w2l, "pre_rnn_chain: W_ih");
+  const bool exact = same_precision({w1, w2}, "pre_rnn_chain");
   TORCH_CHECK(x896.dim() == 2 && bias.numel() == 256, "pre_rnn_chain: x896 (N, K1), bias (256)");
-  int X;
-  if (exact) {
-    TORCH_CHECK(w1h.size(0) == 256 && w1h.size(1) == K1 && w2h.size(1) == 256, "pre_rnn_chain: exact W_pre (256, K1), "
-                "W_ih (X, 256)");
-    X = w2h.size(0);
-  } else {
-    TORCH_CHECK(w1h.dim() == 3 && w1h.size(0) * 32 == K1 && w1h.size(1) == 256 && w1h.size(2) == 32 &&
-                w2h.dim() == 3 && w2h.size(0) == 8 && w2h.size(2) == 32,
-                "pre_rnn_chain: slab-major images (K1/32,256,32) and (8,X,32)");
-    X = w2h.size(1);
-  }
+  const int N = x896.size(0), K1 = x896.size(1), X = (int)w2.rows;
+  TORCH_CHECK(w1.rows == 256 && w1.K == K1 && w2.K == 256, "pre_rnn_chain: W_pre (256, K1), W_ih (X, 256)");
   TORCH_CHECK(K1 % 128 == 0 && X % 128 == 0, "pre_rnn_chain: K1 % 128 == 0 and X % 128 == 0");
   TORCH_CHECK((long long)N * K1 * 4 <= 0x7fff0000LL, "pre_rnn_chain: x896 too large for one launch");
   auto o = x896.options();
   auto x = out_or_new(x_out, {N, 256}, o, "x_out");
   auto xp = out_or_new(xp_out, {N, X}, o, "xp_out");
-  hip_check(dca_dpre_dx(ptr<float>(x896), w1h.data_ptr(), exact ? nullptr : w1l.data_ptr(), ptr<float>(bias),
-                        w2h.data_ptr(), exact ? nullptr : w2l.data_ptr(), ptr<float>(x), ptr<float>(xp), N, K1, X,
-                        exact ? 1 : 0, 1, cur_stream()),
+  hip_check(dca_dpre_dx(ptr<float>(x896), w1.hi, w1.lo, ptr<float>(bias), w2.hi, w2.lo, ptr<float>(x), ptr<float>(xp), N,
+                        K1, X, exact ? 1 : 0, 1, cur_stream()),
             "dca_dpre_dx(forward)");
   return {x, xp};
 }
@@ -1302,9 +1279,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("loss_assemble", &loss_assemble, "loss scalar + metrics from heads/loss partials", py::arg("part"),
         py::arg("norms"), py::arg("N"), py::arg("algo"), py::arg("ent_coef"), py::arg("vf_coef"), py::arg("out"),
         py::arg("S") = 0, py::arg("compat_value_bug") = false);
-  m.def("weight_prep", &weight_prep, "gather the flat fp32 params into bf16 / fp32 working weight images (+ bf16 "
-        "hi / lo split images)", py::arg("src"), py::arg("map16"), py::arg("dst16"), py::arg("map32"), py::arg("dst32"),
-        py::arg("maps") = py::none(), py::arg("dsth") = py::none(), py::arg("dstl") = py::none());
+  m.def("weight_prep", &weight_prep, "gather the flat fp32 params into fp32 working weight images (+ bf16 hi / lo "
+        "split images)", py::arg("src"), py::arg("map32"), py::arg("dst32"), py::arg("maps") = py::none(),
+        py::arg("dsth") = py::none(), py::arg("dstl") = py::none());
   m.def("gemm_tn", &gemm_tn, "C (+)= A^T B for K-outer bf16 or fp32 (bf16x3) operands (split-K MFMA, LDS transposed reads)",
         py::arg("A"), py::arg("B"), py::arg("C"), py::arg("perm") = py::none(), py::arg("accumulate") = false,
         py::arg("B0") = py::none(), py::arg("colsum") = py::none(), py::arg("exact") = false);

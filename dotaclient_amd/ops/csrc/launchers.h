@@ -115,8 +115,8 @@ hipError_t dca_featurize_raw16(const void* raw16, const float* hero, void* units
                                hipStream_t st);
 hipError_t dca_loss_assemble(const float* part, int nrows, const float* norms, int N, int algo, float ent_coef,
                              float vf_coef, float* out, int S, int vbug, hipStream_t st);
-hipError_t dca_weight_prep(const float* src, const int* map16, short* dst16, int n16, const int* map32, float* dst32,
-                           int n32, const int* maps, short* dsth, short* dstl, int ns, hipStream_t st);
+hipError_t dca_weight_prep(const float* src, const int* map32, float* dst32, int n32, const int* maps, short* dsth,
+                           short* dstl, int ns, hipStream_t st);
 
 void dca_gemm_tn_plan(int M, int N, int K, int* splits, int* kc, int* tiles, int f32);
 hipError_t dca_gemm_tn(const void* A, int lda, const void* B, int ldb, const void* B0, int split_rows, float* C,
