@@ -71,6 +71,22 @@
 // 212 vs 201 VGPRs), not of deferring the stores: an open lead. Backward: dropping its ∂gates store altogether saves
 // 25 µs per call (2086 → 2061 µs, 0.018 µs per step) — less than the call varies between two processes (2086 vs
 // 2132 µs for the same kernel); a deferred form was not built.
+// Wave-private gather and lazy deadline stamp (profiles/recurrence_wave_gather.md; B=8, S=1400, H=512, one box, bitwise
+// equal to the parent everywhere). (A) V1/V2 backward: wave wk polls only the chunks of its own K part, the LDS image
+// of ∂G_{t+1} is wave-private and barrier 1 is gone (one s_barrier per step, red[] double-buffered by step parity).
+// (B) spin_fail read the wall clock at a wait's FIRST failed poll — an s_memrealtime round trip ahead of the second
+// poll round of nearly every step of both kernels; the stamp is now taken at the 256th. Learner step, three alternated
+// runs each, ms: parent 5.435-5.444, A alone 5.326-5.344, B alone 5.322-5.325, A + B 5.165-5.179 (more than the sum of the two; not
+// explained). Standalone calls, µs: forward 2058 → 1930 (B only: the clock read cost ≈0.09 µs per step), backward
+// 2131 → 1983. In the step's timeline: forward 1839 → 1721, backward 2080 → 1927, span 5473 → 5201 µs. The phase
+// stamps (10 ns ticks, and each stamp is itself a clock read) show the backward's barrier-1 phase (120-160 ns) gone
+// but the gather phase 600-680 → 760 ns and barrier 2 40-80 → 160 ns: without barrier 1 the wait for the slowest
+// wave moves to barrier 2; per step 1480 → 1440 ns under the stamps. (C) The same for the one-row V1 forward — every
+// unit-owning wave polling the whole h_{t-1} into its own image (4× the poll reads per CU, 209 vs 199 VGPRs), no
+// s_barrier in the step — was built, bitwise equal, and LEFT OUT: forward 1976 vs 1941 µs per call, learner step
+// 5.216-5.225 vs 5.205-5.224 ms, although under the phase stamps its step looked 80 ns shorter (280 ns at H = 128,
+// where one wave owns every unit and the reads do not multiply: not measured untraced). With 2 / 4 rows per chain the
+// 4× poll registers cost occupancy or spill.
 #include "common.h"
 #include <cstdlib>
 
@@ -192,15 +208,22 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* p, in
 // for runs that share the GPU with another process's kernels). It used to count polls over the whole launch, so a
 // recurrence slowed by co-resident kernels (the node loop's actor graph replays) could trip it with no hand-off ever
 // lost — the cumulative count grows with every step's extra polls (the config-5 loop's one backward timeout, code 2).
-// `spins` restarts at every step (the back-off sleep after 32 polls: within ±0.01 µs of never sleeping).
+// `spins` restarts at every step (the back-off sleep after 32 polls: within ±0.01 µs of never sleeping), and `since`
+// restarts with it as 0 = "not stamped yet". The clock is first read at the wait's 256th failed poll (≈0.1 ms in,
+// nothing against the limit), never between a step's first failed poll and its second: stamping at the first
+// failure put a scalar-memory round trip (s_memrealtime + s_waitcnt lgkmcnt(0)) ahead of the second poll round of
+// nearly every step of both kernels.
 __device__ __forceinline__ bool spin_fail(unsigned& spins, unsigned long long& since, TeamCtl* ctl, unsigned* err,
                                           unsigned code, int knobs) {
   asm volatile("" ::: "memory");        // compiler barrier: re-issue the poll loads every round
-  if (spins++ == 0) since = __builtin_amdgcn_s_memrealtime();
+  ++spins;
   if ((spins & 255u) == 0) {
     if (ld_acq(&ctl->abort) != 0) return true;
     const unsigned long long limit = ((knobs >> 15) & 1) ? 6000000000ull : 200000000ull;
-    if (__builtin_amdgcn_s_memrealtime() - since > limit) {
+    const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+    if (since == 0) {
+      since = now;
+    } else if (now - since > limit) {
       st_rel(err, code);
       st_rel(&ctl->abort, 1u);
       return true;
@@ -434,6 +457,7 @@ __device__ __forceinline__ void lstm_team_fwd_body(
     for (int t = 0; t < S; ++t) {
       const int par = t & 1;
       spins = 0;
+      since = 0;
       TSTAMP(0);
       // ---- prefetch this step's input projection (one 16-B vector per owned (row, unit)). Loading it one step
       // ahead instead measured slower (2.11 vs 1.94 µs per step at B=8, H=512).
@@ -733,7 +757,9 @@ __device__ __forceinline__ void lstm_team_bwd_body(
   constexpr int SP = KSL + 4;
   constexpr int DROW = (4 * H / KSL) * SP;   // V1: floats per row image of dG_{t+1}
   __shared__ __attribute__((aligned(16))) float dgf[V1 ? R * DROW : 4];
-  __shared__ float red[NWK][RB][16 + 1];
+  // partial products of the K parts. V1: R rows, two copies by step parity (see the hazard note in the step loop)
+  constexpr int RR = V1 ? R : RB;
+  __shared__ float red[V1 ? 2 : 1][NWK][RR][16 + 1];
   __shared__ float dbs[RB * U * 4];     // per-(row, unit, gate) bias-gradient sums of a chain
   __shared__ int sh_int;
   __shared__ unsigned sh_epoch;
@@ -839,6 +865,7 @@ __device__ __forceinline__ void lstm_team_bwd_body(
     for (int k = 0; k <= S; ++k) {
       const int t = S - 1 - k;          // step whose gate gradients are produced this iteration (-1: final)
       spins = 0;
+      since = 0;
       TSTAMPB(0);
       // ---- prefetch the saved activations of step t for the owned pairs
       dca::f32x4 gv[NPAIR];
@@ -871,21 +898,29 @@ __device__ __forceinline__ void lstm_team_bwd_body(
       if (k > 0) {
         const unsigned tag = tagbase | (unsigned)(t + 2);
         const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(xg + (size_t)((t + 1) & 1) * Bc * H * CPU_, Bc * H * CPU_ * 16);
-        constexpr int RG = V1 ? R : (F32 ? 4 : 8);         // rows per gather group
+        constexpr int RG = F32 ? 4 : 8;                    // rows per gather group
         constexpr int NL = RG * H * CPU_ / NT;             // chunks per thread per group
-        for (int g0 = 0; g0 < B && !dead; g0 += RG) {
-          const int nck = min(RG, B - g0) * H * CPU_;
-          i32x4 g[NL];
-          bool okc[NL];
+        if constexpr (V1) {
+          // Wave-private gather: wave wk polls, tag-checks and writes to LDS exactly the chunks of ITS K part — for
+          // every row the chunks r ∈ [wk·KW/2, (wk+1)·KW/2), gate columns gc = 2r ∈ [wk·KW, (wk+1)·KW) — which are
+          // the 16 slices (wk·16 + slice)·SP its product reads and nothing else reads. CW chunks per lane per row,
+          // the same count per lane as a tid + NT·i split of the row.
+          constexpr int CW = KW / 128;                     // chunks per lane per row
+          constexpr int NLW = R * CW;
+          static_assert(KW % 128 == 0, "a wave's K part is whole rounds of 64 chunks");
+          const int cw0 = (wv % NWK) * (KW / 2) + lane;    // this lane's first chunk of a row
+          i32x4 g[NLW];
+          bool okc[NLW];
 #pragma unroll
-          for (int i = 0; i < NL; ++i) okc[i] = tid + NT * i >= nck;
+          for (int i = 0; i < NLW; ++i) okc[i] = i / CW >= B;
           while (true) {
 #pragma unroll
-            for (int i = 0; i < NL; ++i)
-              if (!okc[i]) g[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (g0 * H * CPU_ + tid + NT * i) * 16, 0, kSc1);
+            for (int i = 0; i < NLW; ++i)
+              if (!okc[i])
+                g[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, ((i / CW) * H * CPU_ + cw0 + 64 * (i % CW)) * 16, 0, kSc1);
             bool ok = true;
 #pragma unroll
-            for (int i = 0; i < NL; ++i) {
+            for (int i = 0; i < NLW; ++i) {
               okc[i] = okc[i] || (((unsigned)g[i].y == tag) & ((unsigned)g[i].w == tag));
               ok &= okc[i];
             }
@@ -893,36 +928,84 @@ __device__ __forceinline__ void lstm_team_bwd_body(
             if (spin_fail(spins, since, ctl, err, 2u, knobs)) { dead = true; break; }
           }
 #pragma unroll
-          for (int i = 0; i < NL; ++i) {
-            const int ci = tid + NT * i;
-            if (ci < nck) {
-              if constexpr (V1) {
-                const int b = ci / (H * CPU_), r = ci % (H * CPU_), gc = 4 * (r >> 1) + 2 * (r & 1);
-                *reinterpret_cast<float2*>(&dgf[b * DROW + (gc / KSL) * SP + gc % KSL]) =
-                    make_float2(__int_as_float(g[i].x), __int_as_float(g[i].z));
-              } else if constexpr (F32) {
-                const int b = g0 + ci / (2 * H), r = ci % (2 * H), gc = 4 * (r >> 1) + 2 * (r & 1);
-                const float x = __int_as_float(g[i].x), z = __int_as_float(g[i].z);
-                const short xh = dca::f2bf(x), zh = dca::f2bf(z);
-                *reinterpret_cast<unsigned*>(&dgl[b][gc]) = (unsigned)(unsigned short)xh | ((unsigned)(unsigned short)zh << 16);
-                *reinterpret_cast<unsigned*>(&dglo[b][gc]) =
-                    (unsigned)(unsigned short)dca::f2bf(x - dca::bf2f(xh)) |
-                    ((unsigned)(unsigned short)dca::f2bf(z - dca::bf2f(zh)) << 16);
-              } else {
-                const int b = g0 + ci / H, j = ci % H;
-                *reinterpret_cast<u32x2*>(&dgl[b][4 * j]) = u32x2{(unsigned)g[i].x, (unsigned)g[i].z};
+          for (int i = 0; i < NLW; ++i) {
+            if (i / CW < B) {
+              const int r = cw0 + 64 * (i % CW), gc = 4 * (r >> 1) + 2 * (r & 1);
+              *reinterpret_cast<float2*>(&dgf[(i / CW) * DROW + (gc / KSL) * SP + gc % KSL]) =
+                  make_float2(__int_as_float(g[i].x), __int_as_float(g[i].z));
+            }
+          }
+        } else {
+          for (int g0 = 0; g0 < B && !dead; g0 += RG) {
+            const int nck = min(RG, B - g0) * H * CPU_;
+            i32x4 g[NL];
+            bool okc[NL];
+#pragma unroll
+            for (int i = 0; i < NL; ++i) okc[i] = tid + NT * i >= nck;
+            while (true) {
+#pragma unroll
+              for (int i = 0; i < NL; ++i)
+                if (!okc[i]) g[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (g0 * H * CPU_ + tid + NT * i) * 16, 0, kSc1);
+              bool ok = true;
+#pragma unroll
+              for (int i = 0; i < NL; ++i) {
+                okc[i] = okc[i] || (((unsigned)g[i].y == tag) & ((unsigned)g[i].w == tag));
+                ok &= okc[i];
+              }
+              if (__all(ok)) break;
+              if (spin_fail(spins, since, ctl, err, 2u, knobs)) { dead = true; break; }
+            }
+#pragma unroll
+            for (int i = 0; i < NL; ++i) {
+              const int ci = tid + NT * i;
+              if (ci < nck) {
+                if constexpr (F32) {
+                  const int b = g0 + ci / (2 * H), r = ci % (2 * H), gc = 4 * (r >> 1) + 2 * (r & 1);
+                  const float x = __int_as_float(g[i].x), z = __int_as_float(g[i].z);
+                  const short xh = dca::f2bf(x), zh = dca::f2bf(z);
+                  *reinterpret_cast<unsigned*>(&dgl[b][gc]) = (unsigned)(unsigned short)xh | ((unsigned)(unsigned short)zh << 16);
+                  *reinterpret_cast<unsigned*>(&dglo[b][gc]) =
+                      (unsigned)(unsigned short)dca::f2bf(x - dca::bf2f(xh)) |
+                      ((unsigned)(unsigned short)dca::f2bf(z - dca::bf2f(zh)) << 16);
+                } else {
+                  const int b = g0 + ci / H, j = ci % H;
+                  *reinterpret_cast<u32x2*>(&dgl[b][4 * j]) = u32x2{(unsigned)g[i].x, (unsigned)g[i].z};
+                }
               }
             }
           }
         }
       }
       TSTAMPB(1);
-      if (dead) sh_int = -2;
-      lds_barrier();
-      if (sh_int == -2) break;
-      TSTAMPB(2);
+      if constexpr (V1) {
+        // No workgroup barrier here (the MFMA forms below keep theirs). Hazards:
+        // * dgf: wave wk wrote the slices [wk·16, wk·16 + 16) of every row image from chunks it polled itself, and its
+        //   product below reads exactly those slices — no wave reads another wave's region, so the image is
+        //   wave-private and only the wave's own ds_writes have to land before its ds_reads: lgkmcnt(0). The next
+        //   step's writes follow this step's reads in the same wave's program order.
+        // * red[]: double-buffered by step parity. Without this barrier nothing orders a wave's product of step k + 1
+        //   behind the pair-owning threads' reads of step k: those threads' publish depends on `rec`, but a wave whose
+        //   K part holds none of this workgroup's units completes its next gather on OTHER workgroups' publishes
+        //   alone. So step k + 1 writes red[(k + 1) & 1] while step k's sums may still be read from red[k & 1]; a write
+        //   to red[k & 1] again (step k + 2) lies behind barrier 2 of step k + 1, which every pair-owning thread
+        //   reaches only after its reads of step k returned (lds_barrier waits lgkmcnt(0) first).
+        // * barriers per step: exactly one (barrier 2) for every wave in every iteration — k = 0 (no gather, no
+        //   product), the clean path, a wave whose gather gave up (it skips the product, raises sh_int and still
+        //   arrives), and k = S (dh0). Everybody leaves the loop behind barrier 2 of the same iteration. (sh_int is
+        //   only ever raised, and the launch ends behind it: a wave that read it late — after a dead wave of the NEXT
+        //   iteration raised it — leaves one iteration early, and its team_exit barrier pairs with the others'
+        //   barrier 2.)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      } else {
+        if (dead) sh_int = -2;
+        lds_barrier();
+        if (sh_int == -2) break;
+        TSTAMPB(2);
+      }
       // ---- partial recurrent gradient over this wave's K quarter → red[wv]
+      const int rp = V1 ? (k & 1) : 0;
       if (V1 && k > 0) {
+       if (!dead) {
         const int wk = wv % NWK;
         const int u0 = 16 * (wv / NWK) + 4 * (lane >> 4);
 #pragma unroll
@@ -936,12 +1019,13 @@ __device__ __forceinline__ void lstm_team_bwd_body(
           o2 = row_sum16(o2);
           o3 = row_sum16(o3);
           if ((lane & 15) == 0 && u0 < U) {
-            red[wk][r][u0] = o0;
-            red[wk][r][u0 + 1] = o1;
-            red[wk][r][u0 + 2] = o2;
-            red[wk][r][u0 + 3] = o3;
+            red[rp][wk][r][u0] = o0;
+            red[rp][wk][r][u0 + 1] = o1;
+            red[rp][wk][r][u0 + 2] = o2;
+            red[rp][wk][r][u0 + 3] = o3;
           }
         }
+       }
       } else if (k > 0) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
@@ -966,18 +1050,20 @@ __device__ __forceinline__ void lstm_team_bwd_body(
             }
           }
 #pragma unroll
-          for (int r = 0; r < 4; ++r) red[wv][mt * 16 + kg * 4 + r][col] = acc[r];
+          for (int r = 0; r < 4; ++r) red[0][wv][mt * 16 + kg * 4 + r][col] = acc[r];
         }
       }
       TSTAMPB(3);
+      if (V1 && dead) sh_int = -2;
       lds_barrier();
+      if (V1 && sh_int == -2) break;
       TSTAMPB(4);
       if (t < 0) {
         for (int i = tid; i < B * U; i += NT) {
           const int b = i / U, u = i % U;
           float acc = 0.f;
 #pragma unroll
-          for (int w = 0; w < NWK; ++w) acc += red[w][b][u];
+          for (int w = 0; w < NWK; ++w) acc += red[rp][w][b][u];
           // an episode starting at step 0 never read h0
           dh0[(size_t)(b0 + b) * H + j0 + u] = (rst != nullptr && rst[(size_t)(b0 + b) * sb] != 0) ? 0.f : acc;
         }
@@ -996,7 +1082,7 @@ __device__ __forceinline__ void lstm_team_bwd_body(
             rec = dhn ? dhn[(size_t)(b0 + b) * H + j0 + u] : 0.f;
           } else if (!rnext[i]) {
 #pragma unroll
-            for (int w = 0; w < NWK; ++w) rec += red[w][b][u];
+            for (int w = 0; w < NWK; ++w) rec += red[rp][w][b][u];
           }
           const float ig = gv[i][0], fg = gv[i][1], gg = gv[i][2], og = gv[i][3];
           const float dht = dv[i] + rec;

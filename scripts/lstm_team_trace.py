@@ -74,11 +74,15 @@ def bwd(B=8, H=512, S=200):
     o = {'kernel': 'team_bwd', 'f32': F32, 'B': B, 'H': H}
     o['step_ns'] = med(np.diff(w[..., 0], axis=2))
     o['gather_ns'] = med(w[..., 1] - w[..., 0])
-    o['barrier1_ns'] = med(w[..., 2] - w[..., 1])
-    # kernel events (lstm_team_bwd_body): 0 step start, 1 dG_{t+1} gathered, 2 after barrier, 3 partial recurrent
-    # product done, 4 after the reduction barrier, 6 gate gradients computed + dG_t published + ∂gates stored
-    # (event 5 is not stamped: reading it gave the round-2 trace's garbage ±1e15 values)
-    o['recurrent_dot_ns'] = med(w[..., 3] - w[..., 2])
+    # kernel events (lstm_team_bwd_body): 0 step start, 1 dG_{t+1} gathered, 2 after barrier 1 (MFMA forms only: the
+    # exact-fp32 VALU forms gather wave-privately, have no barrier there and leave event 2 unwritten, so their product
+    # runs from event 1), 3 partial recurrent product done, 4 after the reduction barrier, 6 gate gradients computed +
+    # dG_t published + ∂gates stored (event 5 is not stamped: reading it gave the round-2 trace's garbage ±1e15 values)
+    if (w[..., 2] > 0).all():
+        o['barrier1_ns'] = med(w[..., 2] - w[..., 1])
+        o['recurrent_dot_ns'] = med(w[..., 3] - w[..., 2])
+    else:
+        o['recurrent_dot_ns'] = med(w[..., 3] - w[..., 1])
     o['barrier2_ns'] = med(w[..., 4] - w[..., 3])
     o['gates_publish_ns'] = med(w[..., 6] - w[..., 4])
     last_pub = w[..., 6].max(axis=(0, 1))
