@@ -87,6 +87,21 @@
 // 5.216-5.225 vs 5.205-5.224 ms, although under the phase stamps its step looked 80 ns shorter (280 ns at H = 128,
 // where one wave owns every unit and the reads do not multiply: not measured untraced). With 2 / 4 rows per chain the
 // 4× poll registers cost occupancy or spill.
+// ∂h hand-off in the exact VALU backward (profiles/recurrence_bwd_handoff.md; B=8, S=1400, H=512, one box, bitwise
+// equal to the parent), KEPT: an owner publishes one 8-byte {∂h_t, tag} granule per (row, unit) right behind the
+// reduction barrier — 4 KB written and polled per row and step instead of 16 KB — and lane l of wave wk polls the
+// granule of unit wk·UW + l, computes that unit's four gate gradients from activations it prefetched (tanh ahead of
+// the poll, loads a step ahead behind the gather) and writes them into its wave's dgf slice; the cell-gradient carry
+// is per-lane state, the lanes of the workgroup's own units store ∂gates and keep the bias sums. Backward call 1978 →
+// 1934 µs (−31 ns per step, a fifth of the 0.15-0.3 ms reasoned from the poll bytes: the poll round is not what the
+// gather waits for), learner step 5.159-5.184 → 5.034-5.072 ms, every run below every parent run and the median
+// difference (0.102 ms) four times the parent's spread. The first build ran 2207 µs: the compiler's wait-count merge
+// put an s_waitcnt vmcnt(0) ahead of every step's tanh (a load left pending into the loop) and ahead of the publish
+// (join with the k = 0 path), each draining the activation loads — see the two asm statements in the body. Activation
+// loads at the top of the step instead of a step ahead: 1933 vs 1943 µs, inside the spread of either. The two- and
+// four-row forms were switched too, measured slower in their learner rows (b16 +0.05, b32 +0.32, bptt350 +0.11 ms) and
+// stay on the ∂gates exchange: only the one-row forms hand off ∂h. Re-measured with it: the 8-wave
+// forward <1,4,true,2>, 2047 vs 1930 µs per call, still slower, not switched.
 #include "common.h"
 #include <cstdlib>
 
@@ -102,6 +117,9 @@ constexpr int kThreads = 256;
 constexpr int kSc1 = 16;                // buffer cache policy: sc1 (bypass the CU's L1, served by the XCD L2)
 constexpr int kPlain = 0;               // plain store: write-through L1, line stays in the XCD L2
 constexpr unsigned kSpinLimit = 1u << 22;
+// ∂h hand-off backward: the consumers' saved-activation loads are issued a step ahead, behind the gather (true), or at
+// the top of the step that uses them, ahead of its poll (false)
+constexpr bool kActsAhead = true;
 
 // Persistent control block (one per stream, zero-initialised once, caller-owned). It is SELF-CLEANING: the last
 // workgroup of a launch to exit resets every field and bumps ``epoch``, so a launch never depends on a memset —
@@ -713,6 +731,33 @@ __device__ __forceinline__ void lstm_team_fwd_body(
   }
 }
 
+// ∂L/∂pre-activations {d_i, d_f, d_g, d_o} of one (row, unit) at one step from ∂h_t (`dht`, recurrent part included),
+// the saved activations gv = {i, f, g, o}, tc = tanh(c_t), cpv = c_{t-1}; advances the cell-gradient carry to step
+// t - 1 and adds the four into `sum` (bias gradient). rcur: an episode starts at t (c_{t-1} is not read). The consumer
+// side of the ∂h hand-off. These are the owner-side expressions below (dc = dcarry + dht·og·(1 − tc²), d_i = dc·gg·ig·
+// (1 − ig), ...) in the same order, with the three places where the compiler fuses a multiply into an add there —
+// 1 − tc², the add of dcarry, and the g and o bias sums; NOT 1 − gg², which it packs with 1 − og — written as fmaf
+// and contraction switched off, so that what is computed here does not follow from how this context gets vectorised:
+// bit for bit the owner-side results of every exact VALU form.
+__device__ __forceinline__ dca::f32x4 gate_grads(const dca::f32x4 gv, float tc, float cpv, float dht, bool rcur,
+                                                 float& dcarry, dca::f32x4& sum) {
+#pragma clang fp contract(off)
+  const float ig = gv[0], fg = gv[1], gg = gv[2], og = gv[3];
+  const float dc = __builtin_fmaf(dht * og, __builtin_fmaf(-tc, tc, 1.f), dcarry);
+  const float d_i = dc * gg * ig * (1.f - ig);
+  const float d_f = rcur ? 0.f : dc * cpv * fg * (1.f - fg);
+  const float qg = 1.f - gg * gg, qo = 1.f - og;
+  const float pg = dc * ig, po = dht * tc * og;
+  const float d_g = pg * qg;
+  const float d_o = po * qo;
+  dcarry = rcur ? 0.f : dc * fg;
+  sum[0] += d_i;
+  sum[1] += d_f;
+  sum[2] = __builtin_fmaf(pg, qg, sum[2]);
+  sum[3] = __builtin_fmaf(po, qo, sum[3]);
+  return dca::f32x4{d_i, d_f, d_g, d_o};
+}
+
 // =============================================================================================================
 // Backward (all-gather of dG). Measured: what limits an in-XCD hand-off is the bytes WRITTEN per step (they also
 // leave the XCD), not the bytes read from L2 — a reduce-scatter of B×H partials per workgroup (512 KB per step per
@@ -721,6 +766,8 @@ __device__ __forceinline__ void lstm_team_fwd_body(
 //   dh_{t}[b, J_m] = Σ_gc dG_{t+1}[b, gc] · W_hh[row(gc), J_m]      (gc = 4·j + q unit-major, row = q·H + j)
 // xg (per team): [2 parity][Bc][H] 16-B chunks {bf16 d_i,d_f | tag | bf16 d_g,d_o | tag} (one per (row, unit)).
 // Waves split K = 4H in quarters (W_hhᵀ slice of the owned units in VGPRs); partial tiles are summed via LDS.
+// The dispatched exact VALU forms (HO in the body) write a quarter of that: xg holds [2 parity][Bc][H] 8-byte granules
+// {f32 ∂h_t | tag}, in a prefix of the same buffer, and the gate gradients are recomputed by every consumer wave.
 // =============================================================================================================
 // V1 (F32, one row per chain): the partial recurrent gradient as exact fp32 VALU dot products — lane (u, kg) keeps
 // W_hhᵀ[gc][j0 + u] for its wave's K quarter and k-group as fp32 VGPRs, dG_{t+1} of row 0 sits in LDS in fp32.
@@ -747,6 +794,14 @@ __device__ __forceinline__ void lstm_team_bwd_body(
   constexpr int KSL = KW / 16;          // V1: K slice per lane of a wave's K part
   constexpr int R = V1 ? (1 << ((VAR >> 5) & 3)) : 1;   // V1: rows per chain (VAR bits 5-6: 1, 2, 4)
   constexpr int NPAIR = ((V1 ? R : RB) * U + NT - 1) / NT;
+  // HO: the ∂h hand-off (see the kernel header). The one-row exact VALU forms whose wave covers at most 64 units of K —
+  // one unit per lane. The two- and four-row forms exchange the gate gradients as before: every wave repeating the gate
+  // math of 2 / 4 rows behind its poll measured slower in the learner rows that run them (learner_b16 8.535 → 8.580,
+  // learner_b32 14.506 → 14.829, bptt350_learner 3.736 → 3.843 ms), and the four-row H = 128 form would also take 184
+  // VGPRs against 153 (occupancy 3 → 2). So do the 4-wave H = 512 form (two units per lane, never dispatched for the
+  // backward) and the MFMA forms. The body below is written for R rows.
+  constexpr int UW = KW / 4;            // units per wave's K part
+  constexpr bool HO = V1 && UW <= 64 && R == 1;
   static_assert(!V1 || (F32 && MT == 1), "V1 is the fp32 exact VALU variant");
   static_assert(VV != 2 || H == 512, "V2 is the H = 512 variant");
   // (Measured and removed in round 5: ∂W_hh accumulated inside this recurrence — 128 accumulators per lane on every
@@ -861,17 +916,85 @@ __device__ __forceinline__ void lstm_team_bwd_body(
       const int pi = tid + NT * i;
       dcarry[i] = (pi < B * U && dcn) ? dcn[(size_t)(b0 + pi / U) * H + j0 + pi % U] : 0.f;
     }
+    // HO: lane `lane` of wave wk handles unit cu = wk·UW + lane of every row — it polls that unit's ∂h granule, turns
+    // it into the unit's four gate gradients and writes them into the wave's slice of dgf. Per handled (row, unit):
+    // the saved activations of the step gathered next (cg = gates4, ccv = c, ccp = c of the step before it, ctc =
+    // tanh(ccv)), the cell-gradient carry, and — used by the lanes of this workgroup's own units only — Σ_t ∂gates.
+    constexpr int RH = HO ? R : 1;
+    const int cu = (wv % NWK) * UW + lane;
+    const bool hasu = HO && lane < UW;
+    const bool mine = hasu && cu >= j0 && cu < j0 + U;
+    dca::f32x4 cg[RH], csum[RH];
+    float ccv[RH], ccp[RH], ctc[RH], cdc[RH];
+    bool crc[RH];
+    // saved activations of step s for the handled pairs (ccv is carried over: c of step s was ccp of step s + 1)
+    auto load_acts = [&](int s) {
+#pragma unroll
+      for (int r = 0; r < RH; ++r) {
+        if (r < B && hasu) {
+          const size_t bt = (size_t)(b0 + r) * sb + (size_t)s * st;
+          cg[r] = *reinterpret_cast<const dca::f32x4*>(gates4 + (bt * H + cu) * 4);
+          ccp[r] = s > 0 ? cs[(bt - st) * H + cu] : c0[(size_t)(b0 + r) * H + cu];
+        }
+      }
+    };
+    if constexpr (HO) {
+#pragma unroll
+      for (int r = 0; r < RH; ++r) {
+        const bool on = r < B && hasu;
+        csum[r] = dca::f32x4{0.f, 0.f, 0.f, 0.f};
+        cg[r] = dca::f32x4{0.f, 0.f, 0.f, 0.f};
+        ccp[r] = ctc[r] = 0.f;
+        crc[r] = false;
+        cdc[r] = (on && dcn) ? dcn[(size_t)(b0 + r) * H + cu] : 0.f;
+        ccv[r] = on ? cs[((size_t)(b0 + r) * sb + (size_t)(S - 1) * st) * H + cu] : 0.f;
+        // land this load here: left pending into the step loop, the compiler's wait-count merge at the loop header
+        // takes ccv for a load in flight in EVERY iteration and drains vmcnt — the publish, the ∂L/∂h load and the
+        // activation loads issued a step ahead — in front of each step's tanh and first poll
+        asm volatile("" ::"v"(ccv[r]));
+      }
+    }
     bool dead = false;
     for (int k = 0; k <= S; ++k) {
-      const int t = S - 1 - k;          // step whose gate gradients are produced this iteration (-1: final)
+      const int t = S - 1 - k;          // step whose ∂h (HO) / gate gradients are published this iteration (-1: final)
       spins = 0;
       since = 0;
       TSTAMPB(0);
       // ---- prefetch the saved activations of step t for the owned pairs
       dca::f32x4 gv[NPAIR];
-      float cv[NPAIR], cpv[NPAIR], dv[NPAIR];
+      float cv[NPAIR], cpv[NPAIR], dv[NPAIR], dvl[NPAIR];
       bool rcur[NPAIR], rnext[NPAIR];     // packing: episode starts at t (c_{t-1} unused) / at t+1 (h_t unused by t+1)
-      if (t >= 0) {
+      if constexpr (HO) {
+        // owners: ∂L/∂h_t from above and the start flag of t + 1. Consumers: tanh(c) and the start flag of the step
+        // gathered below (t + 1), and its activations unless they were issued a step ahead.
+        if (t >= 0) {
+#pragma unroll
+          for (int i = 0; i < NPAIR; ++i) {
+            const int pi = tid + NT * i;
+            rnext[i] = false;
+            if (pi < B * U) {
+              const int b = pi / U, u = pi % U;
+              const size_t bt = (size_t)(b0 + b) * sb + (size_t)t * st;
+              dv[i] = dhs[bt * H + j0 + u];
+              if (rl) rnext[i] = t + 1 < S && ((rbits[b * wpr + ((t + 1) >> 5)] >> ((t + 1) & 31)) & 1u);
+              else if (rst != nullptr) rnext[i] = t + 1 < S && rst[bt + st] != 0;
+            }
+          }
+        }
+        if (k > 0) {
+          if constexpr (!kActsAhead) load_acts(t + 1);
+#pragma unroll
+          for (int r = 0; r < RH; ++r) {
+            if (r < B && hasu) {
+              ctc[r] = tanh_<PREC>(ccv[r]);
+              if (rl) crc[r] = (rbits[r * wpr + ((t + 1) >> 5)] >> ((t + 1) & 31)) & 1u;
+              else if (rst != nullptr) crc[r] = rst[(size_t)(b0 + r) * sb + (size_t)(t + 1) * st] != 0;
+            }
+          }
+        } else if constexpr (kActsAhead) {
+          load_acts(t);
+        }
+      } else if (t >= 0) {
 #pragma unroll
         for (int i = 0; i < NPAIR; ++i) {
           const int pi = tid + NT * i;
@@ -900,7 +1023,59 @@ __device__ __forceinline__ void lstm_team_bwd_body(
         const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(xg + (size_t)((t + 1) & 1) * Bc * H * CPU_, Bc * H * CPU_ * 16);
         constexpr int RG = F32 ? 4 : 8;                    // rows per gather group
         constexpr int NL = RG * H * CPU_ / NT;             // chunks per thread per group
-        if constexpr (V1) {
+        if constexpr (HO) {
+          // ∂h hand-off: one 8-byte {∂h_{t+1}, tag} granule per (row, unit), a quarter of the bytes of the gate-gradient
+          // chunks, written and polled. The lane polls the granule of its unit, computes the unit's four gate
+          // gradients (the owner used to, ahead of its publish) and writes them as one 16-byte ds_write into its
+          // wave's slice of dgf — still exactly the columns the wave's product reads and nothing else reads.
+          const __amdgpu_buffer_rsrc_t rh =
+              uniform_rsrc(reinterpret_cast<const char*>(xg) + (size_t)((t + 1) & 1) * Bc * H * 8, Bc * H * 8);
+          u32x2 g[RH];
+          bool okc[RH];
+#pragma unroll
+          for (int r = 0; r < RH; ++r) {
+            okc[r] = r >= B || !hasu;
+            g[r] = u32x2{0u, 0u};
+          }
+          while (true) {
+#pragma unroll
+            for (int r = 0; r < RH; ++r)
+              if (!okc[r]) g[r] = __builtin_amdgcn_raw_buffer_load_b64(rh, (r * H + cu) * 8, 0, kSc1);
+            bool ok = true;
+#pragma unroll
+            for (int r = 0; r < RH; ++r) {
+              okc[r] = okc[r] || g[r].y == tag;
+              ok &= okc[r];
+            }
+            if (__all(ok)) break;
+            if (spin_fail(spins, since, ctl, err, 2u, knobs)) { dead = true; break; }
+          }
+          // The owners' ∂L/∂h_t landed with the poll (returns are in order). Moved to a register the compiler has
+          // seen no load into: the wait it otherwise emits ahead of the publish, at the join with the k = 0 path, is
+          // vmcnt(0) and covers the activation loads issued below.
+#pragma unroll
+          for (int i = 0; i < NPAIR; ++i) asm volatile("v_mov_b32 %0, %1" : "=v"(dvl[i]) : "v"(dv[i]));
+          if (!dead) {
+#pragma unroll
+            for (int r = 0; r < RH; ++r) {
+              if (r < B && hasu) {
+                const dca::f32x4 d =
+                    gate_grads(cg[r], ctc[r], ccp[r], __uint_as_float(g[r].x), crc[r], cdc[r], csum[r]);
+                constexpr int gpl = KSL / 4;                 // units per K slice
+                *reinterpret_cast<dca::f32x4*>(&dgf[r * DROW + (cu / gpl) * SP + (cu % gpl) * 4]) = d;
+                if (mine) {
+                  const size_t bt = (size_t)(b0 + r) * sb + (size_t)(t + 1) * st;
+                  *reinterpret_cast<dca::f32x4*>(dgates4 + (bt * H + cu) * 4) = d;
+                  if (t + 1 == 0) dc0[(size_t)(b0 + r) * H + cu] = cdc[r];
+                }
+                ccv[r] = ccp[r];
+              }
+            }
+            if constexpr (kActsAhead)
+              if (t >= 0) load_acts(t);
+          }
+          TSTAMPB(5);
+        } else if constexpr (V1) {
           // Wave-private gather: wave wk polls, tag-checks and writes to LDS exactly the chunks of ITS K part — for
           // every row the chunks r ∈ [wk·KW/2, (wk+1)·KW/2), gate columns gc = 2r ∈ [wk·KW, (wk+1)·KW) — which are
           // the 16 slices (wk·16 + slice)·SP its product reads and nothing else reads. CW chunks per lane per row,
@@ -1072,6 +1247,30 @@ __device__ __forceinline__ void lstm_team_bwd_body(
       // ---- gate gradients for the owned (row, unit) pairs; publish dG_t, write ∂gates
       const __amdgpu_buffer_rsrc_t ws = uniform_rsrc(xg + (size_t)(t & 1) * Bc * H * CPU_, Bc * H * CPU_ * 16);
       const int tg = (int)(tagbase | (unsigned)(t + 1));
+      if constexpr (HO) {
+        // ---- owners: ∂h_t = ∂L/∂h_t + recurrent part, published at once; the gate gradients are the consumers' work
+        const __amdgpu_buffer_rsrc_t wh =
+            uniform_rsrc(reinterpret_cast<const char*>(xg) + (size_t)(t & 1) * Bc * H * 8, Bc * H * 8);
+#pragma unroll
+        for (int i = 0; i < NPAIR; ++i) {
+          const int pi = tid + NT * i;
+          if (pi < B * U) {
+            const int b = pi / U, u = pi % U;
+            float rec = 0.f;
+            if (k == 0) {
+              rec = dhn ? dhn[(size_t)(b0 + b) * H + j0 + u] : 0.f;
+              // no gather in this iteration: the one publish that waits for memory waits in this branch (see dvl)
+              asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(dvl[i]), "=v"(rec) : "v"(dv[i]), "v"(rec));
+            } else if (!rnext[i]) {
+#pragma unroll
+              for (int w = 0; w < NWK; ++w) rec += red[rp][w][b][u];
+            }
+            const float dht = dvl[i] + rec;
+            __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(dht), (unsigned)tg}, wh, (b * H + j0 + u) * 8, 0,
+                                                  kPlain);
+          }
+        }
+      } else {
 #pragma unroll
       for (int i = 0; i < NPAIR; ++i) {
         const int pi = tid + NT * i;
@@ -1112,15 +1311,22 @@ __device__ __forceinline__ void lstm_team_bwd_body(
           if (t == 0) dc0[(size_t)(b0 + b) * H + j0 + u] = dcarry[i];
         }
       }
+      }
       TSTAMPB(6);
     }
     if (sh_int == -2) return;
     if (dbpart) {
       // bias gradient of this chain for the owned units: Σ over rows (fixed order) of the per-pair sums
+      if constexpr (HO) {
 #pragma unroll
-      for (int i = 0; i < NPAIR; ++i) {
-        const int pi = tid + NT * i;
-        if (pi < B * U) *reinterpret_cast<dca::f32x4*>(&dbs[pi * 4]) = dsum[i];
+        for (int r = 0; r < RH; ++r)
+          if (r < B && mine) *reinterpret_cast<dca::f32x4*>(&dbs[(r * U + cu - j0) * 4]) = csum[r];
+      } else {
+#pragma unroll
+        for (int i = 0; i < NPAIR; ++i) {
+          const int pi = tid + NT * i;
+          if (pi < B * U) *reinterpret_cast<dca::f32x4*>(&dbs[pi * 4]) = dsum[i];
+        }
       }
       __syncthreads();
       for (int o = tid; o < U * 4; o += NT) {
@@ -1212,7 +1418,8 @@ inline void plan(int B, int& nch, int& Bc, int& MT, int f32 = 0) {
   }
 
 // fp32 chains of ≤ 4 rows take the exact VALU variant; at H = 512 the backward takes its 8-wave form V2 (measured
-// B=8, S=1400: backward 2069 vs 2137 µs, while the 8-wave forward was SLOWER, 2056 vs 1778 µs).
+// B=8, S=1400: backward 2069 vs 2137 µs, while the 8-wave forward is SLOWER: 2047 vs 1930 µs per call, re-measured
+// with both builds in one process after the wave-private gather and the ∂h hand-off, profiles/recurrence_bwd_handoff.md).
 inline int use_v1(int f32, int Bc, int H, int backward, int precise) {
   if (!(f32 && Bc <= 4)) return 0;
   const int rows = Bc == 1 ? 0 : (Bc == 2 ? 32 : 64);         // VAR bits 5-6: 2 or 4 rows per chain

@@ -77,14 +77,22 @@ def bwd(B=8, H=512, S=200):
     # kernel events (lstm_team_bwd_body): 0 step start, 1 dG_{t+1} gathered, 2 after barrier 1 (MFMA forms only: the
     # exact-fp32 VALU forms gather wave-privately, have no barrier there and leave event 2 unwritten, so their product
     # runs from event 1), 3 partial recurrent product done, 4 after the reduction barrier, 6 gate gradients computed +
-    # dG_t published + ∂gates stored (event 5 is not stamped: reading it gave the round-2 trace's garbage ±1e15 values)
-    if (w[..., 2] > 0).all():
+    # dG_t published + ∂gates stored (event 5 is not stamped: reading it gave the round-2 trace's garbage ±1e15 values).
+    # The ∂h hand-off forms (the dispatched exact-fp32 VALU forms) stamp in another order: 0 step start, 1 ∂h_{t+1}
+    # granules gathered AND 5 gate gradients computed, written to LDS and (own units) stored (the two stamps follow each
+    # other: the gate-gradient phase lies inside the gather phase, ahead of the product), 3 product done, 4 after the
+    # barrier, 6 ∂h_t published right behind the barrier. Only they write event 5.
+    if (w[..., 5] > 0).all():
+        # (event 1 is stamped right behind event 5 in these forms, so gather_ns above holds poll + gate gradients)
+        o['gather_gate_grads_ns'] = med(w[..., 5] - w[..., 0])
+        o['recurrent_dot_ns'] = med(w[..., 3] - w[..., 1])
+    elif (w[..., 2] > 0).all():
         o['barrier1_ns'] = med(w[..., 2] - w[..., 1])
         o['recurrent_dot_ns'] = med(w[..., 3] - w[..., 2])
     else:
         o['recurrent_dot_ns'] = med(w[..., 3] - w[..., 1])
     o['barrier2_ns'] = med(w[..., 4] - w[..., 3])
-    o['gates_publish_ns'] = med(w[..., 6] - w[..., 4])
+    o['publish_ns' if (w[..., 5] > 0).all() else 'gates_publish_ns'] = med(w[..., 6] - w[..., 4])
     last_pub = w[..., 6].max(axis=(0, 1))
     o['publish_skew_ns'] = med(last_pub - w[..., 6].min(axis=(0, 1)))
     o['publish_to_first_gather_ns'] = med(w[..., 1].min(axis=(0, 1))[1:] - last_pub[:-1])
