@@ -35,7 +35,9 @@ def build_parser():
     ap.add_argument('--broker', type=str, default=None)
     ap.add_argument('--epochs', type=int, default=4)
     ap.add_argument('--seq-per-epoch', type=int, default=16)
-    ap.add_argument('--batch-size', type=int, default=4)
+    ap.add_argument('--batch-size', type=int, default=4,
+                    help='sequences per minibatch and GPU. fp32-exact: any size up to 256 — one chain of up to 8 '
+                         'sequences per XCD team up to 64, queued chains of 8 beyond (ops/lstm.py team_plan)')
     ap.add_argument('--seq-len', type=int, default=256)
     ap.add_argument('--learning-rate', type=float, default=1e-4)
     ap.add_argument('--entropy-coef', type=float, default=0.01)
@@ -57,7 +59,8 @@ def build_parser():
     ap.add_argument('--async-checkpoint', type=int, default=1,
                     help='publish the model first, write checkpoint files on a background thread')
     ap.add_argument('--precision', type=str, default='fp32-exact', choices=['fp32-exact', 'fp32', 'bf16'],
-                    help='fp32-exact = the reference training precision (IEEE fp32 products on f32 MFMA / VALU); '
+                    help='fp32-exact = the reference training precision (IEEE fp32 products on f32 MFMA / VALU), at every '
+                         'batch size up to 256 sequences per GPU; '
                          'fp32 = fp32 activations with bf16x3-split MFMA operands; bf16 = bf16 GEMM operands '
                          '(the 5v5 entity-attention policy runs fp32 or bf16)')
     ap.add_argument('--pack-sequences', type=str2bool, default=False,

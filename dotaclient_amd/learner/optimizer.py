@@ -232,13 +232,9 @@ class DotaOptimizer:
                         offpolicy=cfg.replay_offpolicy if (replay_on and not self.vtrace_step) else 'clip',
                         vtrace=self.vtrace_step,
                         vtrace_rho_bar=cfg.vtrace_rho_bar, vtrace_c_bar=cfg.vtrace_c_bar)
-        prec = cfg.precision
-        if prec == 'fp32-exact' and self.device.type == 'cuda' and cfg.batch_size > 32:
-            # the exact VALU recurrence runs 1 / 2 / 4 sequences per XCD chain (8 teams): at most 32 per minibatch
-            logger.info('fp32-exact takes at most 32 sequences per minibatch and GPU: training at fp32 with bf16x3 '
-                        'operands (batch_size %d)', cfg.batch_size)
-            prec = 'fp32'
-        self.learner = Learner(self.policy, lc, device=self.device, backend=cfg.backend, precision=prec)
+        # (fp32-exact at any batch size: the exact recurrence queues chains of 8 sequences beyond 64 per minibatch and
+        # GPU; a minibatch past its queue bound is refused by the step itself, never retrained at another precision)
+        self.learner = Learner(self.policy, lc, device=self.device, backend=cfg.backend, precision=cfg.precision)
         if cfg.graph:
             self.learner.enable_graph(warmup=1)
         if trainer_state is not None:

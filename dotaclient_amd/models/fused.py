@@ -24,6 +24,9 @@ Precision (``FusedPolicy(precision=...)``):
 
 * ``'fp32-exact'`` (the learner default, the reference's fp32 training, optimizer.py:281, policy.py:52-78): every
   product an IEEE fp32 FMA (``v_mfma_f32_16x16x4_f32`` / fp32 VALU), fp32 activations, gradients and accumulation.
+  Any number of sequences per step and GPU up to 256: the recurrence runs them as exact VALU chains of 1, 2, 4 or 8
+  rows, one per XCD team up to 64 sequences and queued chains of 8 beyond (``ops.lstm.team_plan(B, True, True)``;
+  a larger step raises before anything is launched — it is never run at another precision).
 * ``'fp32'``: fp32 activations; the hand-written MFMA kernels split each fp32 operand into a hi and a lo bf16 and
   sum hi·hi + lo·hi + hi·lo (≈2⁻¹⁶ relative per product, "bf16x3").
 * ``'bf16'`` has no kernel path (:meth:`use_pipeline` is False): the learner runs it on the torch backend under bf16

@@ -32,7 +32,7 @@ from typing import Dict, NamedTuple, Optional
 
 import torch
 
-from ..ops.lstm import team_bwd, team_fwd
+from ..ops.lstm import team_bwd, team_fwd, team_plan
 from .policy import TYPE_SUFFIX
 
 LDZ = 160
@@ -272,7 +272,7 @@ def _forward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], units_t
     if not lin:
         with torch.cuda.stream(sL):
             team_fwd(C, xp.view(S, B, H, 4), W['rec_w'], h0, c0, fp.err, False, time_major=True, hs_out=hs,
-                     cs_out=cs, gates_out=gates4, bias4=W['rec_b'], reset=rst)
+                     cs_out=cs, gates_out=gates4, bias4=W['rec_b'], reset=rst, exact=exact)
         main.wait_stream(sL)
     # heads GEMM on the chain kernel's stages (bf16x3 images, or exact: fp32 W_cat padded to 256 rows)
     z = C.rowmm_out256(hs.view(N, H), *W['heads_w'], W['heads_b'])   # (N, 256), padding columns 0
@@ -369,7 +369,7 @@ def _backward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], f: For
     with torch.cuda.stream(sL):
         if not lin:
             db = team_bwd(C, hd.dxh, f.gates4, f.cs, c0, None, None, W['rec_w'], fp.err, time_major=True,
-                          dg_out=dgates, dg_bf16=False, want_dbias=True, reset=rst)[3]
+                          dg_out=dgates, dg_bf16=False, want_dbias=True, reset=rst, exact=exact)[3]
             bwd_done = torch.cuda.Event()
             bwd_done.record(sL)
         # the heads' weight gradient waits behind the backward recurrence (off the path between the two recurrences)
@@ -484,10 +484,10 @@ def fused_step_tm(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], un
     weight-gradient GEMMs (W_hh, W_ih, pre-RNN) ACCUMULATE straight into those and are left out of ``grads``.
     Returns (partials (R,16) f32, logp (N) f32 time-major, grads {param name → tensor})."""
     assert fp.fp32, 'the fused step runs at fp32 / fp32-exact (bf16: torch backend)'
-    if fp.exact and B > 32 and fp.cfg.rnn == 'lstm':
-        # lstm_team.hip plan(): the sequences run as chains of ≤ 4 rows (one XCD team each) on the exact fp32 VALU
-        # recurrence; more than 4 rows per chain take the bf16x3 MFMA team kernel — not IEEE fp32
-        raise ValueError(f'fp32-exact: at most 32 sequences per step and GPU (got {B}); use precision fp32')
+    if fp.exact and fp.cfg.rnn == 'lstm':
+        # lstm_team.hip plan_exact(): the sequences run as chains of ≤ 8 rows (one XCD team each) on the exact fp32 VALU
+        # recurrence at every B; beyond 64 the chains queue, and the queue holds 32 (raises here, ahead of any launch)
+        team_plan(B, True, True)
     # sequence packing (learner/ingest.py): per-(step, row) episode-start flags, time-major (S, B) u8 — the team
     # recurrence zeroes h, c before a flagged step (forward) and stops the gradient there (backward)
     rst = reset_t.reshape(S, B) if reset_t is not None else None

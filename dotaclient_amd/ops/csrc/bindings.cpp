@@ -225,13 +225,20 @@ inline void check_ctl(const torch::Tensor& ctl) {
               "team control block too small (use ops.lstm.team_ctl())");
 }
 
+// exact / rows (lstm_team.hip plan_exact): refused here, before any allocation or launch, when they name no plan
+inline void check_team_plan(int B, bool f32w, bool exact, int64_t rows, const char* who) {
+  TORCH_CHECK(rows >= 0 && rows <= 8 && dca_lstm_team_chains(B, f32w ? 1 : 0, exact ? 1 : 0, (int)rows) >= 0, who,
+              ": no launch plan for B = ", B, ", exact = ", exact, ", rows = ", rows,
+              " (rows in {0, 1, 2, 4, 8} and only with exact; exact needs fp32 weights and a queue of ≤ 32 chains)");
+}
+
 std::vector<torch::Tensor> lstm_team_fwd(torch::Tensor xp4, torch::Tensor whh, torch::Tensor h0, torch::Tensor c0,
                                          torch::Tensor err, torch::Tensor ctl, bool want_f32_h,
                                          c10::optional<torch::Tensor> trace,
                                          bool time_major, c10::optional<torch::Tensor> hs_out,
                                          c10::optional<torch::Tensor> cs_out, c10::optional<torch::Tensor> gates_out,
                                          c10::optional<torch::Tensor> bias4, bool precise,
-                                         c10::optional<torch::Tensor> reset) {
+                                         c10::optional<torch::Tensor> reset, bool exact, int64_t rows) {
   CHECK_F32(xp4); CHECK_DEV(whh); CHECK_CONTIG(whh); CHECK_F32(h0); CHECK_F32(c0); CHECK_I32(err); check_ctl(ctl);
   const bool f32w = whh.scalar_type() == at::kFloat;
   TORCH_CHECK(f32w || whh.scalar_type() == at::kBFloat16, "whh must be bf16 or f32");
@@ -255,7 +262,8 @@ std::vector<torch::Tensor> lstm_team_fwd(torch::Tensor xp4, torch::Tensor whh, t
     TORCH_CHECK(bias4->numel() == 4 * H, "bias4 must hold 4H floats (unit-major)");
     bias_p = ptr<float>(*bias4);
   }
-  const size_t wsb = dca_lstm_team_workspace(B, H, 0, f32w ? 1 : 0);
+  check_team_plan(B, f32w, exact, rows, "lstm_team_fwd");
+  const size_t wsb = dca_lstm_team_workspace(B, H, 0, f32w ? 1 : 0, exact ? 1 : 0, (int)rows);
   auto ws = torch::empty({(int64_t)wsb}, f32.dtype(at::kByte));
   hip_check(dca_lstm_team_fwd(ptr<float>(xp4), whh.data_ptr(), ptr<float>(h0), ptr<float>(c0),
                               f32w ? nullptr : ptr<short>(hs),
@@ -263,7 +271,7 @@ std::vector<torch::Tensor> lstm_team_fwd(torch::Tensor xp4, torch::Tensor whh, t
                               ptr<float>(gates4), ptr<float>(hn), ptr<float>(cn), ctl.data_ptr(), ws.data_ptr(), wsb,
                               ptr<unsigned>(err), B, S, H, time_major ? 1 : 0, cur_stream(),
                               trace_ptr(trace, kTeamTraceElems, "lstm_team_fwd"),
-                              bias_p, f32w ? 1 : 0, precise ? 1 : 0, reset_ptr(reset, B, S)),
+                              bias_p, f32w ? 1 : 0, precise ? 1 : 0, reset_ptr(reset, B, S), exact ? 1 : 0, (int)rows),
             "dca_lstm_team_fwd");
   if (f32w) return {hs, hs, cs, gates4, hn, cn};
   return {hs, want_f32_h ? hsf : hs, cs, gates4, hn, cn};
@@ -274,7 +282,8 @@ std::vector<torch::Tensor> lstm_team_bwd(torch::Tensor dhs, torch::Tensor gates4
                                          c10::optional<torch::Tensor> dcn, torch::Tensor whh, torch::Tensor err,
                                          torch::Tensor ctl, c10::optional<torch::Tensor> trace, bool time_major,
                                          c10::optional<torch::Tensor> dg_out, bool dg_bf16, bool want_dbias,
-                                         bool precise, c10::optional<torch::Tensor> reset) {
+                                         bool precise, c10::optional<torch::Tensor> reset, bool exact,
+                                         int64_t rows) {
   CHECK_F32(dhs); CHECK_F32(gates4); CHECK_F32(cs); CHECK_F32(c0); CHECK_DEV(whh); CHECK_CONTIG(whh); CHECK_I32(err);
   check_ctl(ctl);
   const bool f32w = whh.scalar_type() == at::kFloat;
@@ -299,8 +308,10 @@ std::vector<torch::Tensor> lstm_team_bwd(torch::Tensor dhs, torch::Tensor gates4
   auto dh0 = torch::empty({B, H}, f32);
   auto dc0 = torch::empty({B, H}, f32);
   // per-chain bias-gradient partials (Σ over the chain's rows and steps), summed in chain order below
-  torch::Tensor dbp = want_dbias ? torch::empty({dca_lstm_team_chains(B, f32w ? 1 : 0), 4 * H}, f32) : torch::Tensor();
-  const size_t wsb = dca_lstm_team_workspace(B, H, 1, f32w ? 1 : 0);
+  check_team_plan(B, f32w, exact, rows, "lstm_team_bwd");
+  torch::Tensor dbp = want_dbias ? torch::empty({dca_lstm_team_chains(B, f32w ? 1 : 0, exact ? 1 : 0, (int)rows), 4 * H}, f32)
+                                 : torch::Tensor();
+  const size_t wsb = dca_lstm_team_workspace(B, H, 1, f32w ? 1 : 0, exact ? 1 : 0, (int)rows);
   auto ws = torch::empty({(int64_t)wsb}, f32.dtype(at::kByte));
   hip_check(dca_lstm_team_bwd(ptr<float>(dhs), ptr<float>(gates4), ptr<float>(cs), ptr<float>(c0), dhn_p, dcn_p,
                               whh.data_ptr(), dg_bf16 ? nullptr : ptr<float>(dgates4), ptr<float>(dh0),
@@ -308,7 +319,7 @@ std::vector<torch::Tensor> lstm_team_bwd(torch::Tensor dhs, torch::Tensor gates4
                               time_major ? 1 : 0, cur_stream(),
                               trace_ptr(trace, kTeamTraceElems, "lstm_team_bwd"),
                               dg_bf16 ? ptr<short>(dgates4) : nullptr, want_dbias ? ptr<float>(dbp) : nullptr,
-                              f32w ? 1 : 0, precise ? 1 : 0, reset_ptr(reset, B, S)),
+                              f32w ? 1 : 0, precise ? 1 : 0, reset_ptr(reset, B, S), exact ? 1 : 0, (int)rows),
             "dca_lstm_team_bwd");
   if (want_dbias) return {dgates4, dh0, dc0, dbp.sum(0)};
   return {dgates4, dh0, dc0};
@@ -1242,14 +1253,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("xp4"), py::arg("whh"), py::arg("h0"), py::arg("c0"), py::arg("err"), py::arg("ctl"),
         py::arg("want_f32_h"), py::arg("trace") = py::none(), py::arg("time_major") = false, py::arg("hs_out") = py::none(),
         py::arg("cs_out") = py::none(), py::arg("gates_out") = py::none(), py::arg("bias4") = py::none(),
-        py::arg("precise") = false, py::arg("reset") = py::none());
+        py::arg("precise") = false, py::arg("reset") = py::none(), py::arg("exact") = false, py::arg("rows") = 0);
   m.def("lstm_team_bwd", &lstm_team_bwd, "XCD-team persistent LSTM backward (L2-local reduce-scatter)",
         py::arg("dhs"), py::arg("gates4"), py::arg("cs"), py::arg("c0"), py::arg("dhn"), py::arg("dcn"),
         py::arg("whh"), py::arg("err"), py::arg("ctl"), py::arg("trace") = py::none(),
         py::arg("time_major") = false, py::arg("dg_out") = py::none(), py::arg("dg_bf16") = false,
-        py::arg("want_dbias") = false, py::arg("precise") = false, py::arg("reset") = py::none());
-  m.def("lstm_team_chains", [](int64_t B, bool f32) { return dca_lstm_team_chains((int)B, f32 ? 1 : 0); },
-        "sequence chains of a team-recurrence launch of B sequences", py::arg("B"), py::arg("f32"));
+        py::arg("want_dbias") = false, py::arg("precise") = false, py::arg("reset") = py::none(),
+        py::arg("exact") = false, py::arg("rows") = 0);
+  m.def("lstm_team_chains",
+        [](int64_t B, bool f32, bool exact, int64_t rows) {
+          const int n = (rows >= 0 && rows <= 8) ? dca_lstm_team_chains((int)B, f32 ? 1 : 0, exact ? 1 : 0, (int)rows) : -1;
+          TORCH_CHECK(n >= 0, "lstm_team_chains: no launch plan for B = ", B, ", exact = ", exact, ", rows = ", rows);
+          return n;
+        },
+        "sequence chains of a team-recurrence launch of B sequences", py::arg("B"), py::arg("f32"),
+        py::arg("exact") = false, py::arg("rows") = 0);
+  m.def("lstm_team_workspace",
+        [](int64_t B, int64_t H, bool backward, bool f32, bool exact, int64_t rows) {
+          return (int64_t)dca_lstm_team_workspace((int)B, (int)H, backward ? 1 : 0, f32 ? 1 : 0, exact ? 1 : 0, (int)rows);
+        },
+        "exchange-buffer bytes of a team-recurrence launch (0: no such plan)", py::arg("B"), py::arg("H"),
+        py::arg("backward"), py::arg("f32"), py::arg("exact") = false, py::arg("rows") = 0);
   m.def("sample_actions", &sample_actions, "fused masked hierarchical Gumbel-max action sampling (actor)");
   m.def("actor_state_prep", &actor_state_prep, "actor step: state resets + [x | bf16(h)] gate-GEMM operand",
         py::arg("pre"), py::arg("h"), py::arg("c"), py::arg("keep"), py::arg("xh"), py::arg("bump") = py::none());

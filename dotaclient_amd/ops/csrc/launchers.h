@@ -68,18 +68,22 @@ hipError_t dca_encoder_bwd(const float* units, const float* w1, const float* b1,
                            hipStream_t st, const void* demb_in, int f32);
 
 size_t dca_lstm_team_ctl_bytes();
-size_t dca_lstm_team_workspace(int B, int H, int backward, int f32);
+// exact = 1 (fp32 weights only): the fp32-exact plan — exact VALU chains of 1/2/4/8 rows at every B, queued beyond 8
+// chains, a queue of ≤ 32 chains; rows (1, 2, 4, 8; needs exact) forces the rows per chain. A launch that is no valid plan
+// returns hipErrorInvalidValue before anything runs (workspace 0, chains -1).
+size_t dca_lstm_team_workspace(int B, int H, int backward, int f32, int exact = 0, int rows = 0);
 hipError_t dca_lstm_team_fwd(const float* xp4, const void* whh, const float* h0, const float* c0, short* hs,
                              float* hsf, float* cs, float* gates4, float* hn, float* cn, void* ctl, void* ws,
                              size_t ws_bytes, unsigned* err, int B, int S, int H, int time_major, hipStream_t st,
                              unsigned long long* trace, const float* bias4, int f32, int precise = 0,
-                             const unsigned char* rst = nullptr);
-int dca_lstm_team_chains(int B, int f32);
+                             const unsigned char* rst = nullptr, int exact = 0, int rows = 0);
+int dca_lstm_team_chains(int B, int f32, int exact = 0, int rows = 0);
 hipError_t dca_lstm_team_bwd(const float* dhs, const float* gates4, const float* cs, const float* c0,
                              const float* dhn, const float* dcn, const void* whh, float* dgates4, float* dh0,
                              float* dc0, void* ctl, void* ws, size_t ws_bytes, unsigned* err, int B, int S, int H,
                              int time_major, hipStream_t st, unsigned long long* trace, short* dg16, float* dbpart,
-                             int f32, int precise = 0, const unsigned char* rst = nullptr);
+                             int f32, int precise = 0, const unsigned char* rst = nullptr, int exact = 0,
+                             int rows = 0);
 
 hipError_t dca_sample_actions(const float* z, int ldz, const void* emb, int emb_f32, const void* handles, int h32,
                               int N, int U, unsigned long long seed, const long long* ctr, int* idx,

@@ -8,6 +8,9 @@
 // sequence chain and exchanges through that XCD's shared L2: plain stores keep the lines in L2 and sc1 polls (L1
 // bypass, L2-served) see them ≈0.2 µs later (scripts/ubench/xcd_pingpong.hip: 451 ns round trip same-XCD vs
 // 768 ns cross-XCD, idle). Up to 8 teams (one per XCD) run independent chains of ≤ 32 sequences concurrently.
+// The fp32-exact learner's launches (`exact`, plan_exact) stay on the exact fp32 VALU forms at every batch size:
+// chains of 1, 2, 4 or 8 rows, one per team up to 64 sequences, queued chains of 8 rows beyond, 32 chains at the most
+// (kMaxQueue, at make_tagbase) = 256 sequences per launch.
 //
 // Team formation is placement-robust: every workgroup reads HW_REG_XCC_ID and takes a ticket on its XCC's
 // counter; the first 32 of an XCC form its team, a leader commits the team only when all 32 arrived (bounded
@@ -102,6 +105,22 @@
 // four-row forms were switched too, measured slower in their learner rows (b16 +0.05, b32 +0.32, bptt350 +0.11 ms) and
 // stay on the ∂gates exchange: only the one-row forms hand off ∂h. Re-measured with it: the 8-wave
 // forward <1,4,true,2>, 2047 vs 1930 µs per call, still slower, not switched.
+// Eight rows per chain and the exact plan beyond 32 sequences (profiles/exact_big_batch.md; H = 512, one box, three
+// alternated runs per form in one process, µs per forward / backward call), KEPT as the default for 5-8 rows per chain:
+// every run of the 8-row form is below every run of 4-row chains queued two deep. 64 × 1400: 7652-7665 / 7529-7534
+// against 9739-9750 / 8362-8373; 64 × 350: 1936-1940 / 1917-1921 against 2458-2460 / 2126-2128; 64 × 175: 970-973 /
+// 948-950 against 1198-1199 / 1033-1036; 40 × 1400 as 8 chains of 5 rows (the plan's choice): 5755-5761 / 5376-5387
+// against 9699-9721 / 8320-8342 for 10 chains of 4 (and 7826-7871 / 7658-7734 as 5 full chains of 8: live rows, not
+// the form, set the step). The step is VALU / LDS bound and grows by ≈0.5 µs per row: 5.47 µs forward at 8 rows, 3.48
+// at 4, 1.4 at 1. The 8-row forward goes through its rows one at a time (dot products → activations → the select of
+// what the lane stores) instead of holding every row's pre-activations, activations, c and h: 256 VGPRs + 155 AGPRs →
+// 256 + 76 at H = 512, 256 + 66 → 230 + 0 at H = 256, 256 + 12 → 176 + 0 at H = 128 (occupancy 1 → 2 at both), no
+// scratch anywhere; the 50 instantiations that existed before kept every register, SGPR and LDS figure. Its 8-wave
+// form <1,4,true,98> went from 68 bytes of scratch to 211 VGPRs without any, but its one run (a knob, 40 × 24) was 24 %
+// off the float64 recurrence while bitwise self-consistent — the 8-wave forward has never been dispatched at any row
+// count and stays compiled but unselected. Learner step (bench.py, unchanged): 64 × 1400 25.73-25.79 ms (3.47-3.48 M
+// samples/s), 40 × 1400 17.93-17.95 ms (3.12 M), 64 × 175 3.42-3.43 ms (3.27 M); the headline (8 × 1400, plan
+// unchanged) 5.071 / 5.084 / 5.113 ms against the parent's 5.077 / 5.086 / 5.107 in alternation.
 #include "common.h"
 #include <cstdlib>
 
@@ -340,6 +359,16 @@ __device__ void team_exit(TeamCtl* ctl, unsigned* err, int nch) {
   }
 }
 
+// Queue depth. A hand-off tag is {epoch: 11 bits | (iter + 1) mod 32: 5 bits | step + 1: 16 bits}, iter counting the
+// chains THIS team has pulled in the launch. A team that drains a queue of nch chains alone (no other team formed)
+// runs iter = 0 … nch - 1, and the 5-bit field is different for any two of them exactly while nch ≤ 32: then no
+// granule written anywhere in the launch can carry the tag another of its chains waits for, whatever the slots hold
+// (rows a partial chain left unwritten, a chain cut short). At nch = 33, iter 0 and iter 32 share every tag. (With
+// every chain writing all Bc rows and all S steps, a slot polled in iter i was last written in iter i - 1, whose
+// field differs at any depth — but that argument leans on the chains being alike; the bound below leans on nothing.)
+// The field value 0 (iter = 31) cannot match zero-initialised memory either: step + 1 ≥ 1. The exact plan refuses
+// launches of more than kMaxQueue chains (plan_exact): 32 × 8 rows = 256 sequences per launch.
+constexpr int kMaxQueue = 32;
 __device__ __forceinline__ unsigned make_tagbase(unsigned epoch, unsigned iter) {
   return ((epoch & 0x7ffu) << 21) | (((iter + 1u) & 0x1fu) << 16);   // | (t + 1): 16 bits
 }
@@ -376,7 +405,7 @@ __device__ __forceinline__ void lstm_team_fwd_body(
   constexpr int LPU = VV == 2 ? 32 : 16;          // V1/V2: lanes (K slices) per unit
   constexpr int UPW = 64 / LPU;                   // V1/V2: units per wave
   constexpr int KSL = H / LPU;                    // V1/V2: K slice per lane
-  constexpr int R = V1 ? (1 << ((VAR >> 5) & 3)) : 1;   // V1: rows per chain (VAR bits 5-6: 1, 2, 4)
+  constexpr int R = V1 ? (1 << ((VAR >> 5) & 3)) : 1;   // V1: rows per chain (VAR bits 5-6: 1, 2, 4, 8)
   constexpr int NR = V1 ? R : MT;                 // per-lane row registers (V1: every row; MFMA: one per tile)
   static_assert(!V1 || (F32 && MT == 1), "V1 is the fp32 exact VALU variant");
   static_assert(VV != 2 || H == 512, "V2 maps 8 waves x 2 units onto the 16 units of H = 512");
@@ -574,9 +603,33 @@ __device__ __forceinline__ void lstm_team_fwd_body(
        if (mfma_wave) {
         // ---- exact fp32 VALU, R rows: the 4 gates of this lane's unit over its K slice for every row (W_hh slice in
         // VGPRs reused across the rows), summed over the unit's LPU slices — every lane of the group holds every row
-        float g[R][4];
+        float hpub = 0.f;
+        [[maybe_unused]] float ocv = 0.f, ohv = 0.f;
+        [[maybe_unused]] dca::f32x4 oav = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (R == 8) {
+          // 8 rows: one row at a time from the dot products to the select of what this lane stores, so that no
+          // per-row array (pre-activations, activations, c, h: 10 values × 8 rows) is live beside the W_hh slice
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
+          for (int r = 0; r < R; ++r) {
+            if (r < B) {                                      // (B is uniform)
+              float g0, g1, g2, g3;
+              pk_dot4<KSL>(wq, &hf[par][r * ROWF + slice * SP], g0, g1, g2, g3);
+              g0 = row_sum16(g0); g1 = row_sum16(g1); g2 = row_sum16(g2); g3 = row_sum16(g3);
+              if (rzb[r]) { g0 = 0.f; g1 = 0.f; g2 = 0.f; g3 = 0.f; }   // episode start
+              const float pi = g0 + (xv[r][0] + bv[0]), pf = g1 + (xv[r][1] + bv[1]),
+                          pg = g2 + (xv[r][2] + bv[2]), po = g3 + (xv[r][3] + bv[3]);
+              const float ig = sigm<PREC>(pi), fg = sigm<PREC>(pf), gg = tanh_<PREC>(pg), og = sigm<PREC>(po);
+              const float c = fg * (rzb[r] ? 0.f : creg[r]) + ig * gg;
+              const float hv = og * tanh_<PREC>(c);
+              creg[r] = c; hreg[r] = hv;
+              if (slice == r) hpub = hv;
+              if ((slice >> 1) == r) { ocv = c; ohv = hv; oav = dca::f32x4{ig, fg, gg, og}; }
+            }
+          }
+        }
+        float g[R == 8 ? 1 : R][4];
+#pragma unroll
+        for (int r = 0; r < (R == 8 ? 0 : R); ++r) {
           if (r < B) {                                        // (B is uniform)
             pk_dot4<KSL>(wq, &hf[par][r * ROWF + slice * SP], g[r][0], g[r][1], g[r][2], g[r][3]);
             // (Tried, one row: a reduce-SCATTER over the 16 slices — xor 1 / xor 2 quad swaps then row_ror 4 / 8, 4
@@ -586,9 +639,9 @@ __device__ __forceinline__ void lstm_team_fwd_body(
             for (int q = 0; q < 4; ++q) g[r][q] = LPU == 32 ? row_sum32(g[r][q]) : row_sum16(g[r][q]);
           }
         }
-        float act[R][4], cr[R], hr[R], hpub = 0.f;
+        float act[R == 8 ? 1 : R][4], cr[R == 8 ? 1 : R], hr[R == 8 ? 1 : R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
+        for (int r = 0; r < (R == 8 ? 0 : R); ++r) {
           cr[r] = hr[r] = 0.f;
           act[r][0] = act[r][1] = act[r][2] = act[r][3] = 0.f;
           if (r < B) {
@@ -617,8 +670,9 @@ __device__ __forceinline__ void lstm_team_fwd_body(
         if (orow < B && orow < R && !((knobs >> 8) & 1)) {
           float cv = 0.f, hv = 0.f;
           dca::f32x4 av = {0.f, 0.f, 0.f, 0.f};
+          if constexpr (R == 8) { cv = ocv; hv = ohv; av = oav; }
 #pragma unroll
-          for (int r = 0; r < R; ++r)
+          for (int r = 0; r < (R == 8 ? 0 : R); ++r)
             if (orow == r) { cv = cr[r]; hv = hr[r]; av = dca::f32x4{act[r][0], act[r][1], act[r][2], act[r][3]}; }
           const size_t o = ((size_t)(b0 + orow) * sb + (size_t)t * st) * H + eunit;
           gstore((slice & 1) ? hsf + o : cs + o, (slice & 1) ? hv : cv);
@@ -792,7 +846,7 @@ __device__ __forceinline__ void lstm_team_bwd_body(
   constexpr int RB = MT * 16;
   constexpr int GP = 4 * H + 8;         // LDS pitch (bf16) of the gathered dG rows
   constexpr int KSL = KW / 16;          // V1: K slice per lane of a wave's K part
-  constexpr int R = V1 ? (1 << ((VAR >> 5) & 3)) : 1;   // V1: rows per chain (VAR bits 5-6: 1, 2, 4)
+  constexpr int R = V1 ? (1 << ((VAR >> 5) & 3)) : 1;   // V1: rows per chain (VAR bits 5-6: 1, 2, 4, 8)
   constexpr int NPAIR = ((V1 ? R : RB) * U + NT - 1) / NT;
   // HO: the ∂h hand-off (see the kernel header). The one-row exact VALU forms whose wave covers at most 64 units of K —
   // one unit per lane. The two- and four-row forms exchange the gate gradients as before: every wave repeating the gate
@@ -1396,9 +1450,40 @@ inline void plan(int B, int& nch, int& Bc, int& MT, int f32 = 0) {
   MT = Bc <= 16 ? 1 : 2;
 }
 
+// The fp32-exact plan (`exact`): never leaves the exact VALU family, whatever B. As above up to 8 teams × kExactRows
+// rows — one chain per XCD, rows per chain growing through 1, 2, 4, 8 (a chain of 3 or 5-7 rows runs the next form up
+// with its last rows idle) — and value for value the plan above for B ≤ 32. Beyond that, ceil(B / kExactRows) chains
+// of kExactRows rows which queue behind the 8 running ones (the last may be partial). `rows` (1, 2, 4, 8) forces the
+// rows per chain (tests, scripts/exact_rows_bench.py); 0 lets the plan decide. False: not a launch this file runs.
+constexpr int kExactRows = 8;           // rows of the largest exact VALU form
+inline bool plan_exact(int B, int rows, int& nch, int& Bc, int& MT) {
+  if (B < 1 || (rows != 0 && rows != 1 && rows != 2 && rows != 4 && rows != kExactRows)) return false;
+  MT = 1;
+  if (rows != 0) {
+    Bc = rows;
+    nch = (B + rows - 1) / rows;
+  } else if (B <= kMaxTeams * kExactRows) {
+    nch = B < kMaxTeams ? B : kMaxTeams;
+    Bc = (B + nch - 1) / nch;
+  } else {
+    Bc = kExactRows;
+    nch = (B + Bc - 1) / Bc;
+  }
+  return nch <= kMaxQueue;
+}
+
+// One front for every entry point: exact = 0 is plan() and takes no `rows`.
+inline bool plan_any(int B, int f32, int exact, int rows, int& nch, int& Bc, int& MT) {
+  if (exact) return f32 && plan_exact(B, rows, nch, Bc, MT);
+  if (rows != 0) return false;
+  plan(B, nch, Bc, MT, f32);
+  return true;
+}
+
 }  // namespace
 
 // (F32_, V1_) = (0, 0) bf16 MFMA, (1, 0) bf16x3 MFMA, (1, 1) exact-fp32 VALU for one-row chains
+// (V1_ = the kernels' VAR: | 0x20 / 0x40 / 0x60 for 2 / 4 / 8 rows per chain, see use_v1)
 #define DCA_TEAM_DISPATCH(MT_, KS_, F32_, V1_, ...)                                                        \
   switch (((V1_) << 12) | ((F32_) << 8) | ((MT_) << 4) | (KS_)) {                                          \
     case 0x0011: return __VA_ARGS__(1, 1, false, 0); case 0x0012: return __VA_ARGS__(1, 2, false, 0); \
@@ -1414,15 +1499,18 @@ inline void plan(int B, int& nch, int& Bc, int& MT, int f32 = 0) {
     case 0x21114: return __VA_ARGS__(1, 4, true, 33);    case 0x22114: return __VA_ARGS__(1, 4, true, 34);   \
     case 0x41111: return __VA_ARGS__(1, 1, true, 65);    case 0x41112: return __VA_ARGS__(1, 2, true, 65);   \
     case 0x41114: return __VA_ARGS__(1, 4, true, 65);    case 0x42114: return __VA_ARGS__(1, 4, true, 66);   \
+    case 0x61111: return __VA_ARGS__(1, 1, true, 97);    case 0x61112: return __VA_ARGS__(1, 2, true, 97);   \
+    case 0x61114: return __VA_ARGS__(1, 4, true, 97);    case 0x62114: return __VA_ARGS__(1, 4, true, 98);   \
     default: return hipErrorInvalidValue;                                                                    \
   }
 
 // fp32 chains of ≤ 4 rows take the exact VALU variant; at H = 512 the backward takes its 8-wave form V2 (measured
 // B=8, S=1400: backward 2069 vs 2137 µs, while the 8-wave forward is SLOWER: 2047 vs 1930 µs per call, re-measured
 // with both builds in one process after the wave-private gather and the ∂h hand-off, profiles/recurrence_bwd_handoff.md).
-inline int use_v1(int f32, int Bc, int H, int backward, int precise) {
-  if (!(f32 && Bc <= 4)) return 0;
-  const int rows = Bc == 1 ? 0 : (Bc == 2 ? 32 : 64);         // VAR bits 5-6: 2 or 4 rows per chain
+// With `exact` (plan_exact) chains of 5-8 rows take the 8-row form; without it they stay on the bf16x3 MFMA tiles.
+inline int use_v1(int f32, int Bc, int H, int backward, int precise, int exact = 0) {
+  if (!(f32 && Bc <= (exact ? kExactRows : 4))) return 0;
+  const int rows = Bc == 1 ? 0 : (Bc == 2 ? 32 : (Bc <= 4 ? 64 : 96));   // VAR bits 5-6: 2, 4 or 8 rows per chain
   return ((H == 512 && backward) ? 2 : 1) | (precise ? 4 : 0) | rows;
 }
 
@@ -1430,16 +1518,17 @@ inline int use_v1(int f32, int Bc, int H, int backward, int precise) {
 extern "C" size_t dca_lstm_team_ctl_bytes() { return 256; }
 
 // Sequence chains a launch of B sequences is split into (rows of the backward's bias-gradient partials).
-extern "C" int dca_lstm_team_chains(int B, int f32) {
+// -1: not a plan (bad `rows`, `rows` without `exact`, `exact` without fp32 weights, more chains than kMaxQueue).
+extern "C" int dca_lstm_team_chains(int B, int f32, int exact, int rows) {
   int nch, Bc, MT;
-  plan(B, nch, Bc, MT, f32);
+  if (!plan_any(B, f32, exact, rows, nch, Bc, MT)) return -1;
   return nch;
 }
 
 // Exchange-buffer bytes (per-team hand-off rings) for a launch of (B, H). Not zeroed: tags carry the epoch.
-extern "C" size_t dca_lstm_team_workspace(int B, int H, int backward, int f32) {
+extern "C" size_t dca_lstm_team_workspace(int B, int H, int backward, int f32, int exact, int rows) {
   int nch, Bc, MT;
-  plan(B, nch, Bc, MT, f32);
+  if (!plan_any(B, f32, exact, rows, nch, Bc, MT)) return 0;
   if (!backward) return (size_t)kMaxTeams * 2 * Bc * (f32 ? H : H / 2) * 8;
   return (size_t)kMaxTeams * 2 * Bc * H * (f32 ? 2 : 1) * 16;
 }
@@ -1449,13 +1538,14 @@ extern "C" hipError_t dca_lstm_team_fwd(const float* xp4, const void* whh, const
                                         short* hs, float* hsf, float* cs, float* gates4, float* hn, float* cn,
                                         void* ctl_mem, void* ws, size_t ws_bytes, unsigned* err, int B, int S, int H,
                                         int time_major, hipStream_t stream, unsigned long long* trace,
-                                        const float* bias4, int f32, int precise, const unsigned char* rst) {
+                                        const float* bias4, int f32, int precise, const unsigned char* rst,
+                                        int exact, int rows) {
   if (B < 1 || S < 1 || S >= 65535 || (H != 128 && H != 256 && H != 512)) return hipErrorInvalidValue;
-  if (ws_bytes < dca_lstm_team_workspace(B, H, 0, f32) || ctl_mem == nullptr) return hipErrorInvalidValue;
+  int nch, Bc, MT;
+  if (!plan_any(B, f32, exact, rows, nch, Bc, MT)) return hipErrorInvalidValue;
+  if (ws_bytes < dca_lstm_team_workspace(B, H, 0, f32, exact, rows) || ctl_mem == nullptr) return hipErrorInvalidValue;
   if (f32 && hsf == nullptr) return hipErrorInvalidValue;
   if (!f32 && hs == nullptr) return hipErrorInvalidValue;
-  int nch, Bc, MT;
-  plan(B, nch, Bc, MT, f32);
   const int sb = time_major ? 1 : S, st = time_major ? B : 1;   // row(b, t) = b·sb + t·st
   TeamCtl* ctl = reinterpret_cast<TeamCtl*>(ctl_mem);
   unsigned long long* xg = reinterpret_cast<unsigned long long*>(ws);
@@ -1465,7 +1555,7 @@ extern "C" hipError_t dca_lstm_team_fwd(const float* xp4, const void* whh, const
                                                                           hn, cn, xg, ctl, err, B, Bc, nch, S, sb, \
                                                                           st, trace, team_knobs(), bias4, rst),    \
    hipGetLastError())
-  DCA_TEAM_DISPATCH(MT, KS, f32 ? 1 : 0, use_v1(f32, Bc, H, 0, precise), DCA_F)
+  DCA_TEAM_DISPATCH(MT, KS, f32 ? 1 : 0, use_v1(f32, Bc, H, 0, precise, exact), DCA_F)
 #undef DCA_F
 }
 
@@ -1474,13 +1564,13 @@ extern "C" hipError_t dca_lstm_team_bwd(const float* dhs, const float* gates4, c
                                         float* dh0, float* dc0, void* ctl_mem, void* ws, size_t ws_bytes,
                                         unsigned* err, int B, int S, int H, int time_major, hipStream_t stream,
                                         unsigned long long* trace, short* dg16, float* dbpart, int f32, int precise,
-                                        const unsigned char* rst) {
+                                        const unsigned char* rst, int exact, int rows) {
   if (B < 1 || S < 1 || S >= 65534 || (H != 128 && H != 256 && H != 512)) return hipErrorInvalidValue;
   if (dgates4 == nullptr && dg16 == nullptr) return hipErrorInvalidValue;
   if (f32 && dgates4 == nullptr) return hipErrorInvalidValue;
-  if (ws_bytes < dca_lstm_team_workspace(B, H, 1, f32) || ctl_mem == nullptr) return hipErrorInvalidValue;
   int nch, Bc, MT;
-  plan(B, nch, Bc, MT, f32);
+  if (!plan_any(B, f32, exact, rows, nch, Bc, MT)) return hipErrorInvalidValue;
+  if (ws_bytes < dca_lstm_team_workspace(B, H, 1, f32, exact, rows) || ctl_mem == nullptr) return hipErrorInvalidValue;
   const int sb = time_major ? 1 : S, st = time_major ? B : 1;
   TeamCtl* ctl = reinterpret_cast<TeamCtl*>(ctl_mem);
   i32x4* xb = reinterpret_cast<i32x4*>(ws);
@@ -1491,6 +1581,6 @@ extern "C" hipError_t dca_lstm_team_bwd(const float* dhs, const float* gates4, c
                                                                           nch, S, sb, st, trace, dg16, dbpart,      \
                                                                           team_knobs(), rst),                      \
    hipGetLastError())
-  DCA_TEAM_DISPATCH(MT, KS, f32 ? 1 : 0, use_v1(f32, Bc, H, 1, precise), DCA_B)
+  DCA_TEAM_DISPATCH(MT, KS, f32 ? 1 : 0, use_v1(f32, Bc, H, 1, precise, exact), DCA_B)
 #undef DCA_B
 }

@@ -5,6 +5,8 @@
   activated gates and cell states for the backward;
 * ``team_bwd`` — the reverse recurrence in one launch (``_C.lstm_team_bwd``) producing ∂L/∂gates for every step (the
   weight gradients are the learner's split-K GEMMs, ops/csrc/gemm_tn.hip);
+* ``team_plan`` — how a launch splits its sequences into chains (the mirror of the launcher's plan; ``exact=True`` is
+  the fp32-exact plan, which keeps every batch size on the exact VALU forms);
 * ``gate_perm`` / ``team_ctl`` — the gate-major → unit-major row permutation and the per-stream control block;
 * ``parse_team_stats`` / ``merge_team_stats`` — the decoder of the recurrence's telemetry block (did every XCD team
   form, how were the chains spread, how long did the call take on the device; layout below). The kernels do not write
@@ -136,10 +138,53 @@ def merge_team_stats(parsed) -> dict:
     return out
 
 
-def team_fwd(C, xp4, whh16, h0, c0, err, want_f32_h, **kw):
+TEAMS = 8                              # XCD teams of a launch (lstm_team.hip kMaxTeams)
+EXACT_ROWS = (1, 2, 4, 8)              # rows per chain of the exact VALU forms the build dispatches
+EXACT_MAX_CHAINS = 32                  # queue bound of the exact plan (lstm_team.hip kMaxQueue, at make_tagbase)
+EXACT_MAX_BATCH = EXACT_MAX_CHAINS * EXACT_ROWS[-1]
+
+
+def team_plan(B: int, f32: bool, exact: bool, rows: int = 0):
+    """``(nch, Bc)`` of a team-recurrence launch of ``B`` sequences: the pure-Python mirror of lstm_team.hip
+    ``plan()`` / ``plan_exact()``. Chain ``c`` holds the sequences ``[c·Bc, min((c + 1)·Bc, B))`` (empty where that
+    range is); a chain of ``Bc`` rows runs the next kernel form up (1, 2, 4, 8 rows).
+
+    ``exact`` (fp32 weights only) is the fp32-exact plan: exact VALU chains at every ``B`` — one chain per XCD team
+    while ``B`` ≤ 8 × 8, then ``ceil(B / 8)`` queued chains of 8 rows, at most ``EXACT_MAX_CHAINS`` of them. ``rows``
+    (only with ``exact``) forces the rows per chain. Raises ``ValueError`` for what the launcher refuses."""
+    B, rows = int(B), int(rows)
+    if B < 1:
+        raise ValueError(f'team_plan: B = {B}')
+    if not exact:
+        if rows != 0:
+            raise ValueError('team_plan: rows needs exact')
+        nch = min(B, TEAMS) if B <= TEAMS * 32 else (B + 31) // 32
+        if f32 and (B + nch - 1) // nch > 16:       # fp32 MFMA chains hold at most 16 rows
+            nch = (B + 15) // 16
+        return nch, (B + nch - 1) // nch
+    if not f32:
+        raise ValueError('team_plan: exact needs fp32 weights')
+    if rows != 0 and rows not in EXACT_ROWS:
+        raise ValueError(f'team_plan: rows = {rows}, not one of 0, {", ".join(map(str, EXACT_ROWS))}')
+    rmax = EXACT_ROWS[-1]
+    if rows != 0:
+        nch, Bc = (B + rows - 1) // rows, rows
+    elif B <= TEAMS * rmax:
+        nch = min(B, TEAMS)
+        Bc = (B + nch - 1) // nch
+    else:
+        nch, Bc = (B + rmax - 1) // rmax, rmax
+    if nch > EXACT_MAX_CHAINS:
+        raise ValueError(f'team_plan: {nch} chains of {Bc} rows for B = {B}, the exact plan queues at most '
+                         f'{EXACT_MAX_CHAINS} (B ≤ {EXACT_MAX_CHAINS * (rows or rmax)})')
+    return nch, Bc
+
+
+def team_fwd(C, xp4, whh16, h0, c0, err, want_f32_h, exact=False, rows=0, **kw):
     return C.lstm_team_fwd(xp4, whh16, h0.contiguous(), c0.contiguous(), err, team_ctl(xp4.device), want_f32_h,
-                           **kw)
+                           exact=exact, rows=rows, **kw)
 
 
-def team_bwd(C, dhs, gates4, cs, c0, dhn, dcn, whh16, err, **kw):
-    return C.lstm_team_bwd(dhs, gates4, cs, c0.contiguous(), dhn, dcn, whh16, err, team_ctl(dhs.device), **kw)
+def team_bwd(C, dhs, gates4, cs, c0, dhn, dcn, whh16, err, exact=False, rows=0, **kw):
+    return C.lstm_team_bwd(dhs, gates4, cs, c0.contiguous(), dhn, dcn, whh16, err, team_ctl(dhs.device),
+                           exact=exact, rows=rows, **kw)
