@@ -6,7 +6,7 @@ h/c) lives on the GPU in fixed slots and one step of *all* slots is a captured g
 
     H2D(env, units, handles, keep)           pinned → static device buffers (one copy each)
     encoder_fwd                              fused entity encoder kernel (shared with the learner)
-    [5v5: attn_block_fwd                     LayerNorm + QKV + attention + out-projection + pools, one kernel]
+    [5v5: attn_block_act                     LayerNorm + QKV + attention + out-projection + pools, one kernel]
     actor_core                               ONE kernel (ops/csrc/actor_core.hip): episode resets (h, c *= keep),
                                              relu(x896·W_preᵀ + b), gates = [x | h]·[W_ih | W_hh]ᵀ + b + LSTM cell
                                              (or the fake_rnn Linear), z = h·W_headsᵀ + b for all 5 heads
@@ -118,10 +118,12 @@ class GpuActorPolicy:
     """Fixed-slot batched policy step on one GPU: LSTM / linear-RNN policies, 1v1 or 5v5 (entity attention), bf16
     operands on hand-written MFMA kernels (``CORE_MODE`` 1; :class:`F32ActorPolicy` is the IEEE-fp32 twin).
 
-    ``n_sets > 1`` (1v1 policies): the policy holds ``n_sets`` weight versions (``load_weights(state, set=k)``) and
-    every slot steps on the version ``h_set[slot]`` names — still one encoder, one core and one sampler launch: the
-    kernels' 16-row tiles are gathered from slots that share a set (:func:`build_set_plan`, rebuilt when ``h_set``
-    changed). A slot changes its set together with a reset of its state."""
+    ``n_sets > 1`` (1v1 policies; 5v5 on :class:`F32ActorPolicy`): the policy holds ``n_sets`` weight versions
+    (``load_weights(state, set=k)``) and every slot steps on the version ``h_set[slot]`` names — still one encoder,
+    one core and one sampler launch: the kernels' 16-row tiles are gathered from slots that share a set
+    (:func:`build_set_plan`, rebuilt when ``h_set`` changed); the 5v5 attention block runs one workgroup per slot and
+    takes the slot's set directly (the plan's ``slot_set`` region). A slot changes its set together with a reset of
+    its state."""
 
     CORE_MODE = 1        # ops/csrc/actor_core.hip: 0 = IEEE fp32 (f32 MFMA), 1 = bf16 operands
 
@@ -133,8 +135,9 @@ class GpuActorPolicy:
         self.n_sets = int(n_sets)
         if self.n_sets < 1:
             raise ValueError('n_sets must be >= 1')
-        if self.n_sets > 1 and policy.config.entity_attention:
-            raise ValueError('n_sets > 1: the entity-attention (5v5) step runs one weight version per launch')
+        if self.n_sets > 1 and policy.config.entity_attention and self.CORE_MODE != 0:
+            raise ValueError('n_sets > 1: the bf16 entity-attention (5v5) step runs one weight version per launch '
+                             '(its fp32-output bf16x3 encoder has no mixed-set form; F32ActorPolicy covers 5v5)')
         if self.n_sets > 1 and inputs_from is not None:
             raise ValueError('n_sets > 1: a mixed step stages its own observations (no inputs_from)')
         # raw: observations staged as compact raw unit records (features/raw.py, 32 B per unit slot + a 16 B hero
@@ -184,6 +187,11 @@ class GpuActorPolicy:
             self.h_plan_rows, self.h_tile_set = self.in_pack.host['rows'], self.in_pack.host['tile_set']
             self._in_last = 'tile_set'
             self._plan_kw = {'rows': self.in_pack.dev['rows'], 'tile_set': self.in_pack.dev['tile_set']}
+            self.h_slot_set = None
+            if self.cfg.entity_attention:
+                # the attention block runs one workgroup per slot: it takes the slot's set as it is
+                self.h_slot_set = self.in_pack.host['slot_set']
+                self._in_last = 'slot_set'
             self._planned = None
             self._plan()
         self.d_env = self.in_pack.dev['env']
@@ -235,13 +243,18 @@ class GpuActorPolicy:
         if self.n_sets == 1:
             return []
         T = plan_tiles(self.n, self.n_sets)
-        return [('rows', (16 * T,), torch.int32), ('tile_set', (T,), torch.int32)]
+        fields = [('rows', (16 * T,), torch.int32), ('tile_set', (T,), torch.int32)]
+        if self.cfg.entity_attention:
+            fields.append(('slot_set', (self.n,), torch.int32))
+        return fields
 
     def _plan(self):
         """Rebuild the launch plan in the staging pack if ``h_set`` changed since the last step."""
         h = self.h_set.numpy()
         if self._planned is None or not np.array_equal(h, self._planned):
             build_set_plan(h, self.n_sets, self.h_plan_rows.numpy(), self.h_tile_set.numpy())
+            if self.h_slot_set is not None:
+                self.h_slot_set.numpy()[:] = h              # validated by build_set_plan
             self._planned = h.copy()
 
     def _alloc_state(self):
@@ -356,7 +369,7 @@ class GpuActorPolicy:
             w['bqkv'] = g('entity_attn.qkv.bias').contiguous()
             # W_qkv / W_out in MFMA fragment order (ops/csrc/attn_block.hip, as the learner): hi / lo bf16 images
             # (bf16x3 block), or — the IEEE-fp32 actor, mode 0 — the fp32 image and an empty lo (the exact block
-            # kernel attn_block_fwd_f32_kernel<true>, the fp32-exact learner's forward)
+            # kernel attn_block_fwd_f32_kernel<true, ·>, the fp32-exact learner's forward)
             for key, name in (('wq', 'entity_attn.qkv.weight'), ('wo', 'entity_attn.out.weight')):
                 if mode == 0:
                     w[key + '_h'], w[key + '_l'] = _frag_order(g(name).contiguous()), g(name).new_empty(0)
@@ -391,16 +404,19 @@ class GpuActorPolicy:
         C, w, cfg = self.C, self.w, self.cfg
         if self.raw:
             C.featurize_raw(self.d_raw, self.d_hero, self.d_units, self.d_handles)
-        x896, emb, arg = C.encoder_fwd(self.d_units, self.d_env, w['w1'], w['b1'], w['wt'], w['bt'], w['we'],
+        x896, emb, _ = C.encoder_fwd(self.d_units, self.d_env, w['w1'], w['b1'], w['wt'], w['bt'], w['we'],
                                        w['be'], list(cfg.layout.counts), bool(cfg.compat_bugs),
                                        exact=self.CORE_MODE == 0, **self._plan_kw)
         if cfg.entity_attention:
             # 5v5 pre-LN self-attention over the 64 unit slots + pools of the attended embeddings, ONE kernel
-            # (ops/csrc/attn_block.hip, the learner's forward); E1 is the pointer head's unit embedding
-            out = C.attn_block_fwd(emb.view(self.n * self.U, 128), w['bout'], w['ln_g'], w['ln_b'], w['wq_h'],
-                                   w['wq_l'], w['bqkv'], w['wo_h'], w['wo_l'], self.toff, x896, arg,
-                                   bool(cfg.compat_bugs), 1e-5)
-            emb = out[6].view(self.n, self.U, 128)
+            # (ops/csrc/attn_block.hip, the learner's forward in its actor form: bitwise its E1 and pools, nothing
+            # saved for a backward); E1 is the pointer head's unit embedding. Mixed step: one workgroup per slot,
+            # on the slot's own weight set
+            row_set = self.in_pack.dev['slot_set'] if self.n_sets > 1 else None
+            e1 = C.attn_block_act(emb.view(self.n * self.U, 128), w['bout'], w['ln_g'], w['ln_b'], w['wq_h'],
+                                  w['wq_l'], w['bqkv'], w['wo_h'], w['wo_l'], self.toff, x896,
+                                  bool(cfg.compat_bugs), 1e-5, row_set=row_set, n_sets=self.n_sets)
+            emb = e1.view(self.n, self.U, 128)
         elif cfg.compat_bugs:
             x896[:, 768:896] = x896[:, 512:640]
         C.actor_core(x896, w['cpre'], w['bpre'], w['cg'], w['bg'], w['ch'], w['bh'], self.h, self.c,
@@ -560,9 +576,9 @@ class GpuActorPolicy:
 class F32ActorPolicy(GpuActorPolicy):
     """:class:`GpuActorPolicy` at the reference actor's precision (agent.py:641-660 → policy.py:80-84, torch fp32):
     the IEEE-fp32 entity encoder (``encoder_fwd`` exact: the learner's ``encoder_fwd_x_kernel``), for the 5v5 policy
-    the IEEE-fp32 attention block (``attn_block_fwd`` with fp32 fragment images: the fp32-exact learner's block
-    forward), and the fp32 ``actor_core`` (every product an fp32 FMA on ``v_mfma_f32_16x16x4_f32``), fp32 unit
-    embeddings into the sampler. LSTM-128 / LSTM-512 / 5v5, or the compat linear layer."""
+    the IEEE-fp32 attention block (``attn_block_act`` with fp32 fragment images: the fp32-exact learner's block
+    forward without its saved activations), and the fp32 ``actor_core`` (every product an fp32 FMA on
+    ``v_mfma_f32_16x16x4_f32``), fp32 unit embeddings into the sampler. LSTM-128 / LSTM-512 / 5v5, or the compat linear layer."""
 
     CORE_MODE = 0
 

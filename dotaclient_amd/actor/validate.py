@@ -83,7 +83,8 @@ def evaluate_vs_snapshot(policy, snapshot_state, n_games: int = 64, device='cuda
     ``latest_weights_prob`` 0: one team — Radiant or Dire at random — plays the snapshot, the other the current
     weights; reference mini-league, agent.py:760-765); a fixed ``seed`` replays the same openings. Returns
     ``win_rate`` (wins + ½ time-limit draws, per game), ``wins`` / ``losses`` / ``draws`` and ``games``.
-    ``league_step='mixed'``: both versions in ONE policy step per group (VecActor ``league_step``) instead of two."""
+    ``league_step='mixed'``: both versions in ONE policy step per group (VecActor ``league_step``) instead of two —
+    every 1v1 policy, and the 5v5 policy at ``precision='fp32'`` (this function's default)."""
     from .league import League
     from .vec import VecActor
     from .weights import WeightStore
@@ -120,7 +121,8 @@ def league_matrix(snapshots, config, n_games: int = 32, device='cuda', seed: int
                   threads: int = 8, precision: str = 'fp32', league_step: str = 'separate') -> Dict[str, object]:
     """Pairwise win rates of league snapshots ``[(label, state_dict), …]`` (oldest first): entry [i][j] is the
     score of snapshot i against snapshot j over ``n_games`` games (wins + ½ draws; [j][i] = 1 − [i][j]). A healthy
-    league is (mostly) increasing along each row's diagonal direction: later snapshots beat earlier ones."""
+    league is (mostly) increasing along each row's diagonal direction: later snapshots beat earlier ones.
+    ``league_step='mixed'`` (1v1, and 5v5 at ``precision='fp32'``): one policy step per group for both snapshots."""
     from ..models.policy import Policy
     labels = [lab for lab, _ in snapshots]
     n = len(snapshots)

@@ -23,7 +23,8 @@ drained, and it becomes current. Results are fed back to the league per game.
 ``league_step='mixed'``: instead of extra policies, each group's ONE policy holds three weight sets (0: the latest
 weights, 1-2: the two rotating opponent snapshots) and every slot steps on its game's set in the same launch
 (:class:`~dotaclient_amd.actor.batched.GpuActorPolicy` ``n_sets``): one policy step per group step whatever the
-league does, no second or third pass over all slots and no output splice.
+league does, no second or third pass over all slots and no output splice. Every 1v1 policy; the fused 5v5
+(entity-attention) policy at ``precision='fp32'``.
 """
 from __future__ import annotations
 
@@ -156,9 +157,9 @@ class VecActor:
         # league opponents: their own slot policies ('separate') or weight sets 1-2 of the group's one policy ('mixed')
         if league_step not in LEAGUE_STEPS:
             raise ValueError(f'league_step must be one of {LEAGUE_STEPS}, got {league_step!r}')
-        if league_step == 'mixed' and fused and self.cfg.entity_attention:
-            raise ValueError("league_step='mixed': the fused entity-attention (5v5) step runs one weight version "
-                             "per launch")
+        if league_step == 'mixed' and fused and self.cfg.entity_attention and precision != 'fp32':
+            raise ValueError("league_step='mixed': the fused entity-attention (5v5) step mixes weight versions at "
+                             "precision='fp32' only (the bf16 step's fp32-output encoder has no mixed-set form)")
         self.league_step = league_step
         groups = max(1, min(int(groups), n_games))
         sizes = [n_games // groups + (1 if i < n_games % groups else 0) for i in range(groups)]

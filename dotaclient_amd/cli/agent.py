@@ -60,7 +60,8 @@ def build_parser():
                          'fp8 (e4m3 MFMA kernel; 1v1 LSTM-512 policies)')
     ap.add_argument('--league-step', type=str, default='separate', choices=['separate', 'mixed'],
                     help='vec runtime league opponents: separate = an extra policy step per busy opponent snapshot; '
-                         'mixed = one step per group, every slot on its own weight version (1v1 policies)')
+                         'mixed = one step per group, every slot on its own weight version (1v1 policies; 5v5 with '
+                         '--actor-precision fp32)')
     ap.add_argument('--league', type=str, default='oldest', choices=['oldest', 'uniform', 'recent', 'pfsp'],
                     help='opponent sampling over the weight history when not playing the latest weights')
     return ap

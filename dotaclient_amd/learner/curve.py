@@ -56,7 +56,8 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
     ``replay_recent_frac`` from those newest and the rest by priority over the whole ring (``replay_priority_alpha`` /
     ``replay_priority_eta``, ops/replay.py), ``replay_ratio`` > 1 runs that many times more replay steps per
     iteration. ``league_step='mixed'``: league opponents (the actors' and the snapshot evaluations') are stepped in
-    the same launch as the latest weights (VecActor ``league_step``)."""
+    the same launch as the latest weights (VecActor ``league_step``; a 5v5 policy: fp32 actor / evaluation precision
+    only)."""
     import json
     import os
 

@@ -24,6 +24,7 @@
 // resident set cannot fit at all.
 #include "common.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -48,6 +49,26 @@ struct BlockArgs {
   int compat;
   float scale, eps;
 };
+// the actor form's arguments (ACT): the weight arguments hold n_sets sets back to back (per set 128 / 128 / 128 /
+// 384 / 384·128 / 128·128 elements of bout / gamma / beta / bq / W_qkv / W_out); row n runs on set row_set[n]
+// (nullptr: set 0). xn … lse are unused, arg may be nullptr.
+struct ActArgs : BlockArgs {
+  const int* row_set;
+  int n_sets;
+};
+template <bool ACT, typename T>
+__device__ __forceinline__ T wsel(T act, T learner) {
+  if constexpr (ACT) return act;
+  else return learner;
+}
+__device__ __forceinline__ const float* set_ptr(const float* p, int set, int per_set) {
+  return p + (size_t)set * per_set;
+}
+// a weight image of either precision: per_set elements of fp32 (EX) or bf16
+template <bool EX>
+__device__ __forceinline__ const void* wset_ptr(const void* p, int set, int per_set) {
+  return static_cast<const char*>(p) + (size_t)set * per_set * (EX ? 4 : 2);
+}
 
 __device__ __forceinline__ void split8v(const float* v, bf16x8& hi, bf16x8& lo) {
 #pragma unroll
@@ -197,13 +218,39 @@ __device__ __forceinline__ void iput1(char* img, int i, int col, float v) {
 
 // Two rows in flight per CU (256 VGPRs). (Measured slower and removed: one row per CU with the phase-B weight
 // fragments double-buffered one k-step ahead — 5v5 step 8.45 vs 8.15 ms.) EX: the IEEE-fp32 twin (F8 / F4 above).
-template <bool EX>
-__global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(BlockArgs P) {
+//
+// ACT: the actor's inference form. Nothing is saved for a backward (xn, mu, rs, qkv, o, lse are not stored; the LDS
+// images and registers they were stored from feed the next phases as before), arg is optional, and workgroup n runs
+// on weight set row_set[n] of n_sets sets held back to back in every weight argument (the mixed-version policy step:
+// one workgroup per slot, so a per-slot set is one workgroup-uniform pointer offset). Every expression of the
+// learner form is kept, so E1 and the pools are bitwise its.
+template <bool EX, bool ACT>
+__global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(
+    typename std::conditional<ACT, ActArgs, BlockArgs>::type P) {
   __shared__ __attribute__((aligned(16))) char img[kImgBytes];                   // Xn, then O
   __shared__ __attribute__((aligned(16))) float e1s[kU * kPE];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, kg = lane >> 4, li = lane & 15;
   const int n = blockIdx.x;
   const size_t rbase = (size_t)n * kU;
+  // W(x): weight argument x of this workgroup — its set's part in the actor form (offset once, here), P.x itself
+  // where it is used in the learner form (copies of the pointers made here changed that form's register allocation)
+  [[maybe_unused]] const float *bout = nullptr, *gamma = nullptr, *beta = nullptr, *bq = nullptr;
+  [[maybe_unused]] const void *wqh = nullptr, *wql = nullptr, *woh = nullptr, *wol = nullptr;
+#define W(x) wsel<ACT>(x, P.x)
+  if constexpr (ACT) {
+    // a stale index can never read past an operand: the set is clamped into [0, n_sets)
+    const int set = P.row_set != nullptr ? min(max(P.row_set[n], 0), P.n_sets - 1) : 0;
+    bout = set_ptr(P.bout, set, kD);
+    gamma = set_ptr(P.gamma, set, kD);
+    beta = set_ptr(P.beta, set, kD);
+    bq = set_ptr(P.bq, set, 3 * kD);
+    wqh = wset_ptr<EX>(P.wqh, set, 3 * kD * kD);
+    woh = wset_ptr<EX>(P.woh, set, kD * kD);
+    if constexpr (!EX) {                    // EX has no lo images
+      wql = wset_ptr<EX>(P.wql, set, 3 * kD * kD);
+      wol = wset_ptr<EX>(P.wol, set, kD * kD);
+    }
+  }
 
   // ---- A: LayerNorm, 4 threads per unit row (32 columns each)
   {
@@ -214,10 +261,10 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(BlockArgs P)
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float4 v = *reinterpret_cast<const float4*>(src + 4 * i);
-      x[4 * i] = v.x - P.bout[32 * p + 4 * i];
-      x[4 * i + 1] = v.y - P.bout[32 * p + 4 * i + 1];
-      x[4 * i + 2] = v.z - P.bout[32 * p + 4 * i + 2];
-      x[4 * i + 3] = v.w - P.bout[32 * p + 4 * i + 3];
+      x[4 * i] = v.x - W(bout)[32 * p + 4 * i];
+      x[4 * i + 1] = v.y - W(bout)[32 * p + 4 * i + 1];
+      x[4 * i + 2] = v.z - W(bout)[32 * p + 4 * i + 2];
+      x[4 * i + 3] = v.w - W(bout)[32 * p + 4 * i + 3];
     }
 #pragma unroll
     for (int j = 0; j < 32; ++j) s += x[j];
@@ -234,16 +281,20 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(BlockArgs P)
     q += __shfl_xor(q, 2, 64);
     const float rs = rsqrtf(q * (1.f / kD) + P.eps);
 #pragma unroll
-    for (int j = 0; j < 32; ++j) x[j] = x[j] * rs * P.gamma[32 * p + j] + P.beta[32 * p + j];
-    float* dst = P.xn + (rbase + u) * kD + 32 * p;
+    for (int j = 0; j < 32; ++j) x[j] = x[j] * rs * W(gamma)[32 * p + j] + W(beta)[32 * p + j];
+    if constexpr (!ACT) {
+      float* dst = P.xn + (rbase + u) * kD + 32 * p;
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
-      *reinterpret_cast<float4*>(dst + 4 * i) = make_float4(x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]);
+      for (int i = 0; i < 8; ++i)
+        *reinterpret_cast<float4*>(dst + 4 * i) = make_float4(x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]);
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) iput8<EX>(img, u, 32 * p + 8 * i, x + 8 * i);
-    if (p == 0) {
-      P.mu[rbase + u] = mu;
-      P.rs[rbase + u] = rs;
+    if constexpr (!ACT) {
+      if (p == 0) {
+        P.mu[rbase + u] = mu;
+        P.rs[rbase + u] = rs;
+      }
     }
   }
   __syncthreads();
@@ -269,9 +320,9 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(BlockArgs P)
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       const int rq = kHd * h + 16 * c;
-      const F8<EX> qw = wfrag8<EX>(P.wqh, P.wql, rq, 32 * ks, lane);
-      const F8<EX> kw = wfrag8<EX>(P.wqh, P.wql, 128 + rq, 32 * ks, lane);
-      const F8<EX> vw = wfrag8<EX>(P.wqh, P.wql, 256 + rq, 32 * ks, lane);
+      const F8<EX> qw = wfrag8<EX>(W(wqh), W(wql), rq, 32 * ks, lane);
+      const F8<EX> kw = wfrag8<EX>(W(wqh), W(wql), 128 + rq, 32 * ks, lane);
+      const F8<EX> vw = wfrag8<EX>(W(wqh), W(wql), 256 + rq, 32 * ks, lane);
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
         qt[c][a] = mma8<EX>(qw, xf[a], qt[c][a]);    // m = d (weight row), n = unit
@@ -282,7 +333,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(BlockArgs P)
   }
   }
   // QKV → HBM (no bias): Qᵀ / Kᵀ lanes hold 4 consecutive d of one unit (one 16-B store), V one element
-  {
+  if constexpr (!ACT) {
     float* qb = P.qkv + rbase * 384;
 #pragma unroll
     for (int c = 0; c < 2; ++c)
@@ -305,8 +356,8 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(BlockArgs P)
       f32x4 bqv, bkv;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        bqv[r] = P.bq[kHd * h + 16 * c + 4 * kg + r];
-        bkv[r] = P.bq[128 + kHd * h + 16 * c + 4 * kg + r];
+        bqv[r] = W(bq)[kHd * h + 16 * c + 4 * kg + r];
+        bkv[r] = W(bq)[128 + kHd * h + 16 * c + 4 * kg + r];
       }
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
@@ -325,7 +376,8 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(BlockArgs P)
         for (int c = 0; c < 2; ++c) acc = mma4<EX>(kf[c][b], qf[c][a], acc);
         s[b][a] = acc;
       }
-    float* lse = P.lse + ((size_t)n * 4 + h) * kU;
+    float* lse = nullptr;
+    if constexpr (!ACT) lse = P.lse + ((size_t)n * 4 + h) * kU;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       float m = -INFINITY;
@@ -350,17 +402,20 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(BlockArgs P)
       const float inv = 1.f / sum;
 #pragma unroll
       for (int b = 0; b < 4; ++b) s[b][a] *= inv;
-      if (kg == 0) lse[16 * a + li] = m + (EX ? logf(sum) : __logf(sum));
+      if constexpr (!ACT) {
+        if (kg == 0) lse[16 * a + li] = m + (EX ? logf(sum) : __logf(sum));
+      }
     }
     // O = P·V: A[m = i][k = j] = s[b][a], B[k = j][n = d] = v[b][c] (+ bias of column d)
     F4<EX> vf[4][2];
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      const float bv = P.bq[256 + kHd * h + 16 * c + li];
+      const float bv = W(bq)[256 + kHd * h + 16 * c + li];
 #pragma unroll
       for (int b = 0; b < 4; ++b) vf[b][c] = mk4<EX>(vv[b][c] + bv);
     }
-    float* ob = P.o + rbase * kD;
+    float* ob = nullptr;
+    if constexpr (!ACT) ob = P.o + rbase * kD;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       F4<EX> pf[4];
@@ -375,7 +430,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(BlockArgs P)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int i = 16 * a + 4 * kg + r;
-          ob[(size_t)i * kD + col] = acc[r];
+          if constexpr (!ACT) ob[(size_t)i * kD + col] = acc[r];
           iput1<EX>(img, i, col, acc[r]);
         }
       }
@@ -394,7 +449,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(BlockArgs P)
     for (int ks = 0; ks < 4; ++ks) {
       F8<EX> wf[2];
 #pragma unroll
-      for (int t = 0; t < 2; ++t) wf[t] = wfrag8<EX>(P.woh, P.wol, 16 * (2 * w + t), 32 * ks, lane);
+      for (int t = 0; t < 2; ++t) wf[t] = wfrag8<EX>(W(woh), W(wol), 16 * (2 * w + t), 32 * ks, lane);
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
         const F8<EX> of = ifrag<EX>(img, 16 * a, 32 * ks, lane);
@@ -435,10 +490,11 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_f32_kernel(BlockArgs P)
         }
       }
       P.x896[(size_t)n * 896 + kD + t * kD + c] = m;
-      P.arg[((size_t)n * 6 + t) * kD + c] = (unsigned char)am;
+      if (!ACT || P.arg != nullptr) P.arg[((size_t)n * 6 + t) * kD + c] = (unsigned char)am;
     }
   }
 }
+#undef W
 
 // =============================================================================================================
 // Fused fp32 entity-attention block BACKWARD (gfx950, bf16x3 MFMA): ONE launch per step instead of demb + ∂O GEMM +
@@ -973,8 +1029,27 @@ extern "C" hipError_t dca_attn_block_fwd_f32(const float* e0, const float* bout,
               0.17677669529663687f /* 1/sqrt(32) */, eps};
   for (int i = 0; i < 7; ++i) a.off[i] = off[i];
   if (a.off[6] != kU) return hipErrorInvalidValue;
-  if (exact) hipLaunchKernelGGL(attn_block_fwd_f32_kernel<true>, dim3(N), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(attn_block_fwd_f32_kernel<false>, dim3(N), dim3(256), 0, stream, a);
+  if (exact) hipLaunchKernelGGL((attn_block_fwd_f32_kernel<true, false>), dim3(N), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((attn_block_fwd_f32_kernel<false, false>), dim3(N), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// The actor's inference form of the block: only e1, x896[:, 128:896] and (optionally, arg != nullptr) arg are
+// written. The weight arguments hold n_sets sets back to back; row n takes set row_set[n] (clamped into
+// [0, n_sets)), set 0 when row_set is nullptr.
+extern "C" hipError_t dca_attn_block_act(const float* e0, const float* bout, const float* gamma, const float* beta,
+                                         const void* wqh, const void* wql, const float* bq, const void* woh,
+                                         const void* wol, float* e1, float* x896, unsigned char* arg, const int* off,
+                                         int compat, int N, float eps, hipStream_t stream, int exact,
+                                         const int* row_set, int n_sets) {
+  if (N < 1) return hipSuccess;
+  if (n_sets < 1) return hipErrorInvalidValue;
+  ActArgs a{{e0, bout, gamma, beta, wqh, wql, bq, woh, wol, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, e1,
+             x896, arg, {0}, compat, 0.17677669529663687f /* 1/sqrt(32) */, eps}, row_set, n_sets};
+  for (int i = 0; i < 7; ++i) a.off[i] = off[i];
+  if (a.off[6] != kU) return hipErrorInvalidValue;
+  if (exact) hipLaunchKernelGGL((attn_block_fwd_f32_kernel<true, true>), dim3(N), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((attn_block_fwd_f32_kernel<false, true>), dim3(N), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 

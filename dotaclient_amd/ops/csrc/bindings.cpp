@@ -699,6 +699,48 @@ static void check_type_off(const std::vector<int64_t>& t) {
   for (int i = 0; i < 6; ++i) TORCH_CHECK(t[i + 1] >= t[i], "type offsets must be non-decreasing");
 }
 
+// The actor's inference form of the block (attn_block.hip, ACT): → e1 only; the pools go into x896[:, 128:896] and,
+// when given, arg (N, 6, 128). Nothing is saved for a backward. The weights hold n_sets sets back to back (leading
+// dimension); row n runs on set row_set[n] (int32 (N), clamped into [0, n_sets) on the device), set 0 without row_set.
+torch::Tensor attn_block_act(torch::Tensor e0, torch::Tensor bout, torch::Tensor gamma, torch::Tensor beta,
+                             torch::Tensor wqh, torch::Tensor wql, torch::Tensor bq, torch::Tensor woh,
+                             torch::Tensor wol, std::vector<int64_t> type_off, torch::Tensor x896, bool compat,
+                             double eps, c10::optional<torch::Tensor> row_set, int64_t n_sets,
+                             c10::optional<torch::Tensor> arg) {
+  CHECK_F32(e0); CHECK_F32(bout); CHECK_F32(gamma); CHECK_F32(beta); CHECK_F32(bq); CHECK_F32(x896);
+  TORCH_CHECK(n_sets >= 1, "attn_block_act: n_sets >= 1");
+  const int64_t S = n_sets;
+  const Operand wq = operand(wqh, wql, S * 384 * 128, "attn_block_act: W_qkv"),
+                wo = operand(woh, wol, S * 128 * 128, "attn_block_act: W_out");
+  const bool exact = same_precision({wq, wo}, "attn_block_act");
+  TORCH_CHECK(e0.numel() % (64 * 128) == 0 && e0.size(-1) == 128, "attn_block_act: e0 (N·64, 128)");
+  const int64_t N = e0.numel() / (64 * 128);
+  TORCH_CHECK(bq.numel() == S * 384 && bout.numel() == S * 128 && gamma.numel() == S * 128 &&
+              beta.numel() == S * 128, "attn_block_act: weight shapes (n_sets sets back to back)");
+  TORCH_CHECK(x896.dim() == 2 && x896.size(0) == N && x896.size(1) == 896, "attn_block_act: x896 (N, 896)");
+  check_type_off(type_off);
+  const int* rs = nullptr;
+  if (row_set && row_set->defined()) {
+    CHECK_I32(*row_set);
+    TORCH_CHECK(row_set->numel() == N, "attn_block_act: row_set (N)");
+    rs = ptr<int>(*row_set);
+  }
+  unsigned char* ap = nullptr;
+  if (arg && arg->defined()) {
+    CHECK_U8(*arg);
+    TORCH_CHECK(arg->numel() == N * 6 * 128, "attn_block_act: arg (N, 6, 128)");
+    ap = ptr<unsigned char>(*arg);
+  }
+  int off[7];
+  for (int i = 0; i < 7; ++i) off[i] = (int)type_off[i];
+  auto e1 = torch::empty({N * 64, 128}, e0.options());
+  hip_check(dca_attn_block_act(ptr<float>(e0), ptr<float>(bout), ptr<float>(gamma), ptr<float>(beta), wq.hi, wq.lo,
+                               ptr<float>(bq), wo.hi, wo.lo, ptr<float>(e1), ptr<float>(x896), ap, off,
+                               compat ? 1 : 0, (int)N, (float)eps, cur_stream(), exact ? 1 : 0, rs, (int)S),
+            "dca_attn_block_act");
+  return e1;
+}
+
 // Fused fp32 entity-attention block backward (attn_block.hip). q = the heads' z rows (row stride q.stride(0)), dx =
 // ∂x896; o / qkv / lse / mu / rs from attn_block_fwd, e0 = E0' (N·64, 128); W_outᵀ images in 16x16x32 fragment
 // order, W_qkv images in 16x16x16 B-fragment order (bf16 hi / lo). Returns (∂E1, ∂QKV (no bias), ∂E0,
@@ -1296,6 +1338,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tile_set") = py::none());
   m.def("attn_block_fwd", &attn_block_fwd, "fused fp32 entity-attention block forward: LN + QKV + attention + "
         "out-projection + residual + pools (-> xn, mean, rstd, qkv, o, lse, e1)");
+  m.def("attn_block_act", &attn_block_act, "actor (inference) form of the entity-attention block forward: e1 and the "
+        "pools only, nothing saved for a backward; optional per-row weight sets (-> e1)", py::arg("e0"),
+        py::arg("bout"), py::arg("gamma"), py::arg("beta"), py::arg("wqh"), py::arg("wql"), py::arg("bq"),
+        py::arg("woh"), py::arg("wol"), py::arg("type_off"), py::arg("x896"), py::arg("compat"), py::arg("eps"),
+        py::arg("row_set") = py::none(), py::arg("n_sets") = 1, py::arg("arg") = py::none());
   m.def("attn_block_bwd", &attn_block_bwd, "fused fp32 entity-attention block backward: demb + dO + attention "
         "backward + dXn + LayerNorm backward (-> de1, dqkv, de0, [dgamma | dbeta | dbt])");
     m.def("loss_prep", &loss_prep, "loss normalisers from one-hot action rows (graph-replayable)");

@@ -13,6 +13,10 @@ hipError_t dca_attn_block_fwd_f32(const float* e0, const float* bout, const floa
                                   const void* wol, float* xn, float* mu, float* rs, float* qkv, float* o, float* lse,
                                   float* e1, float* x896, unsigned char* arg, const int* off, int compat, int N,
                                   float eps, hipStream_t stream, int exact);
+hipError_t dca_attn_block_act(const float* e0, const float* bout, const float* gamma, const float* beta,
+                              const void* wqh, const void* wql, const float* bq, const void* woh, const void* wol,
+                              float* e1, float* x896, unsigned char* arg, const int* off, int compat, int N,
+                              float eps, hipStream_t stream, int exact, const int* row_set, int n_sets);
 int dca_attn_block_bwd_groups(int N);
 hipError_t dca_attn_block_bwd_f32(const float* dtl, const float* q, int ldq, const float* dx, const unsigned char* arg,
                                   const int* off, int compat, const float* o, const float* qkv, const float* bq,

@@ -2,11 +2,13 @@
 
     python3 scripts/league_step_bench.py [n_games] [bf16|fp32|fp8] [latest_weights_prob] [separate|mixed|policy] [steps]
 
-Self-play of ``n_games`` 1v1 lstm512 games against a uniform league over three stored versions; with
+Self-play of ``n_games`` games of the ``PRESET`` policy (environment variable; default lstm512, 1v1; ``5v5``: the
+entity-attention policy in 5v5 games) against a uniform league over three stored versions; with
 ``latest_weights_prob`` 0.0 every game has an opponent team (snapshot evaluation, actor/validate.py), 0.8 is BASELINE
 config 5. Rollouts are published into a list that is dropped. ``DEVICE=cpu`` runs the eager slot policy. Prints one
 JSON line. Run each setting in a fresh process (``separate`` and ``mixed`` alternating) when comparing. ``policy``: the
-policy step alone (see :func:`policy_only`)."""
+policy step alone (see :func:`policy_only`); where the policy refuses a mixed step (5v5 below fp32), ``us_mixed`` is
+null."""
 import json
 import os
 import random
@@ -30,7 +32,9 @@ warmup = 50
 device = torch.device(os.environ.get('DEVICE', 'cuda'))
 sync = (lambda: torch.cuda.synchronize(device)) if device.type == 'cuda' else (lambda: None)
 
-cfg = get_config('lstm512')
+preset = os.environ.get('PRESET', 'lstm512')
+cfg = get_config(preset)
+team = cfg.layout.counts[0]                     # players per team: 1 (1v1 presets) or 5
 
 
 def policy_only():
@@ -82,15 +86,21 @@ def policy_only():
             o.wait()
     t_sep = timed(launch_sep, wait_sep)
     del opps, one
-    mixed = make_slot_policy(pol, n, seed=1, n_sets=3, **kw)
-    fill(mixed)
-    games = n // 2                                                     # a game's two slots: at most one opponent
+    games = n // (2 * team)                                            # a game's two teams: at most one opponent
     opp = np.flatnonzero(rng.random(games) < 1.0 - lwp)
     hs = np.zeros(n, np.int32)
-    hs[2 * opp + rng.integers(0, 2, len(opp))] = rng.integers(1, 3, len(opp))
-    mixed.h_set.numpy()[:] = hs
-    t_mixed = timed(mixed.step_async, mixed.wait)
+    first = team * (2 * opp + rng.integers(0, 2, len(opp)))           # first slot of each opponent team
+    hs[first[:, None] + np.arange(team)] = rng.integers(1, 3, len(opp))[:, None]
+    try:
+        mixed = make_slot_policy(pol, n, seed=1, n_sets=3, **kw)
+    except ValueError:                                                 # no mixed step for this policy / precision
+        t_mixed = None
+    else:
+        fill(mixed)
+        mixed.h_set.numpy()[:] = hs
+        t_mixed = timed(mixed.step_async, mixed.wait)
     print(json.dumps({'policy_only': True, 'precision': precision, 'latest_weights_prob': lwp, 'slots': n,
+                      'preset': preset,
                       'us_single': t_single, 'us_separate_3_policies': t_sep, 'us_mixed': t_mixed,
                       'slots_per_set': np.bincount(hs, minlength=3).tolist()}))
 
@@ -106,7 +116,7 @@ sink = []
 va = VecActor(ws, n_games, lambda b: sink.append(len(b)), device=device, seed=1, threads=int(os.environ.get('THREADS', 8)),
               groups=2, hidden_stride=1400, rollout_size=9999, max_dota_time=600.0, stagger=True, precision=precision,
               latest_weights_prob=lwp, league=League(ws, mode='uniform', rng=random.Random(0)),
-              opponent_refresh=64, league_step=league_step)
+              opponent_refresh=64, league_step=league_step, mode='5v5' if team > 1 else '1v1')
 for _ in range(warmup):
     va.step()
 sync()
