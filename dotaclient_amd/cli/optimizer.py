@@ -90,6 +90,11 @@ def build_parser():
                     help='mixture sampler: priority exponent (0 = uniform over the filled ring)')
     ap.add_argument('--replay-priority-eta', type=float, default=0.9,
                     help='mixture sampler: weight of max|A| against mean|A| in a sequence\'s priority')
+    ap.add_argument('--replay-priority-beta', type=float, default=0.0,
+                    help='mixture sampler: exponent of the importance-sampling weights (N q)^-beta / max on every '
+                         'sampled sequence\'s loss (0 = off; needs --replay-sampler mixture and --algo ppo)')
+    ap.add_argument('--replay-priority-beta-anneal', type=int, default=0,
+                    help='move --replay-priority-beta linearly to 1 over this many iterations (0 = constant)')
     ap.add_argument('--replay-ratio', type=float, default=1.0,
                     help='replay steps per iteration as a multiple (>= 1) of epochs x fresh minibatches')
     ap.add_argument('--prefetch-rollouts', type=int, default=0,
@@ -99,9 +104,22 @@ def build_parser():
     return ap
 
 
+def check_args(ap, args):
+    """Refuse option combinations that have no meaning before anything is set up (``ap.error``: usage + exit 2)."""
+    if not 0.0 <= args.replay_priority_beta <= 1.0 or args.replay_priority_beta_anneal < 0:
+        ap.error('--replay-priority-beta must lie in [0, 1] and --replay-priority-beta-anneal be >= 0')
+    if args.replay_priority_beta > 0 and args.replay_sampler != 'mixture':
+        ap.error('--replay-priority-beta > 0 needs --replay-sampler mixture: the importance-sampling weights correct '
+                 'the prioritised sampler; the uniform sampler has none')
+    if args.replay_priority_beta > 0 and args.algo != 'ppo':
+        ap.error('--replay-priority-beta > 0 needs --algo ppo: the vpg loss has no per-sequence weights')
+
+
 def main(argv=None):
     from ..presets import parse_with_preset
-    args = parse_with_preset(build_parser(), 'optimizer', argv)
+    ap = build_parser()
+    args = parse_with_preset(ap, 'optimizer', argv)
+    check_args(ap, args)
     logging.basicConfig(format='%(asctime)s %(levelname)-8s %(message)s', level=args.log_level)
     import torch
     from ..learner.optimizer import DotaOptimizer, OptimizerConfig
@@ -129,6 +147,8 @@ def main(argv=None):
                           replay_sampler=args.replay_sampler, replay_recent_frac=args.replay_recent_frac,
                           replay_priority_alpha=args.replay_priority_alpha,
                           replay_priority_eta=args.replay_priority_eta, replay_ratio=args.replay_ratio,
+                          replay_priority_beta=args.replay_priority_beta,
+                          replay_priority_beta_anneal=args.replay_priority_beta_anneal,
                           allow_pickle_experience=args.allow_pickle_experience,
                           prefetch_rollouts=args.prefetch_rollouts, pack_sequences=args.pack_sequences)
     broker = make_broker(args.broker or f'tcp://{args.ip}:{args.port}')

@@ -150,9 +150,11 @@ class Learner:
                 adv, ret, extra = self._vtrace_torch(batch, logits, values, masks, actions)
             loss, metrics = ppo_loss(logits, values, actions, masks, adv, ret, batch['logp_old'],
                                      cfg.clip_eps, cfg.entropy_coef, cfg.vf_coef, stable=stable,
-                                     offpolicy=cfg.offpolicy)
+                                     offpolicy=cfg.offpolicy, seq_weight=getattr(self, '_seq_weight', None))
             metrics.update(extra)
             return loss, metrics
+        if getattr(self, '_seq_weight', None) is not None:
+            raise ValueError('per-sequence loss weights (replay priority_beta > 0) are not defined for the VPG loss')
         return vpg_loss(logits, values, actions, masks, batch['norm_ret'], batch['ret'], cfg.entropy_coef,
                         cfg.vf_coef, compat_value_bug=cfg.compat_value_bug, stable=stable)
 
@@ -321,8 +323,15 @@ class Learner:
         computes the sampled sequences' new priorities from its un-normalised V-trace advantages (fused: the
         ``seq_priority`` kernel inside the step, next to the V-trace kernel; torch: ops/replay.py
         ``priority_from_advantages``) and a scatter stores them behind the step, in stream order. The sampler's
-        statistics of this step ride in the returned metrics. Eager and captured steps draw the same index stream."""
+        statistics of this step ride in the returned metrics. Eager and captured steps draw the same index stream.
+        With importance-sampling weights (``replay.weighted``) the same sampling pass writes the draws' weights into
+        the sampler state's fixed buffer; the step reads its first ``B`` entries (``seq_weight``) in the loss. A
+        captured step with weights has a key of its own: its loss kernel is wired to that buffer."""
         update = self.cfg.vtrace and self.cfg.algo == 'ppo'
+        sw = replay.seq_weight(B) if getattr(replay, 'weighted', False) else None
+        if sw is not None and self.cfg.algo != 'ppo':
+            raise ValueError('importance-sampling weights (replay priority_beta > 0) weight the PPO objectives; the '
+                             'VPG loss has no weighted form')
         if not update and replay.priority_alpha > 0:
             raise ValueError("a prioritised replay with priority_alpha > 0 needs the in-step V-trace advantages: "
                              "LossConfig(algo='ppo', vtrace=True) (learner/optimizer.py advantages='vtrace-step')")
@@ -330,16 +339,19 @@ class Learner:
         # (alpha = 0 without the in-step V-trace: every priority stays at its entry value 1 = (·)^0, nothing to store)
         pc = (replay.priority_eta, replay.priority_alpha, replay.priority_eps) if update else None
         self._priority_cfg = pc
+        self._seq_weight = sw
         if fused:
             self.model.priority_cfg = pc
+            self.model.seq_weight = sw
         try:
             if self.direct() and self._graph_ready():
                 if replay.sampler == 'mixture' or getattr(replay, 'host_sampling', False):
                     fill = (lambda static: replay.sample_into(static, recent))
                 else:
                     fill = (lambda static: static.copy_(replay.sample_indices(B, recent)))
-                m = self._step_replay_key(replay, B, lambda: replay.sample_indices(B, recent), fill)
-                idx = self.graphs.static(self.graphs.replay_key(replay, B, replay.S))
+                m = self._step_replay_key(replay, B, lambda: replay.sample_indices(B, recent), fill,
+                                          weighted=sw is not None)
+                idx = self.graphs.static(self._replay_key(replay, B, replay.S, sw is not None))
             else:
                 idx = replay.sample_indices(B, recent)
                 if self.direct():
@@ -348,8 +360,10 @@ class Learner:
                     m = self.train_step(replay.gather(idx))
         finally:
             self._priority_cfg = None
+            self._seq_weight = None
             if fused:
                 self.model.priority_cfg = None
+                self.model.seq_weight = None
         if update:
             # fused: the buffer the step's seq_priority kernel wrote (models/pipelined.py _heads_loss) — the very
             # tensor a captured step is wired to, looked up, never re-made
@@ -357,6 +371,8 @@ class Learner:
         st = replay.sampler_state.stats.clone()     # one copy: the values below are views of it
         m['replay/recent_draws'], m['replay/age_sum'], m['replay/priority_sum'] = st[0], st[1], st[2]
         m['replay/priority_max'] = st[3]
+        if sw is not None:
+            m['replay/is_weight_sum'], m['replay/is_weight_min'], m['replay/zero_prob_draws'] = st[4], st[5], st[6]
         return m
 
     def train_step_indices(self, replay, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -369,11 +385,17 @@ class Learner:
             return self._step_replay_key(replay, idx.numel(), lambda: idx, lambda static: static.copy_(idx))
         return self._finish(self._direct_body(self.gather_time_major(replay, idx, replay.S), idx.numel(), replay.S))
 
-    def _step_replay_key(self, replay, B: int, indices, fill) -> Dict[str, torch.Tensor]:
+    def _replay_key(self, replay, B: int, S: int, weighted: bool = False):
+        """Graph-cache key of a step on ``replay``; a step whose loss reads per-sequence weights never shares one
+        with a step that does not."""
+        key = self.graphs.replay_key(replay, B, S)
+        return key + ('is_weight',) if weighted else key
+
+    def _step_replay_key(self, replay, B: int, indices, fill, weighted: bool = False) -> Dict[str, torch.Tensor]:
         """Captured step on ``B`` sequences of ``replay``: the key's static input is its index buffer, a copy of
         ``indices()`` when the key is new and written by ``fill`` from then on."""
         S = replay.S
-        return self._finish(self._captured(self.graphs.replay_key(replay, B, S), lambda: indices().clone(), fill,
+        return self._finish(self._captured(self._replay_key(replay, B, S, weighted), lambda: indices().clone(), fill,
                                            lambda sidx: (self.gather_time_major(replay, sidx, S), B, S)))
 
     def _sync_and_step(self):

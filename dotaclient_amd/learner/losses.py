@@ -17,7 +17,7 @@ functions are its oracle.
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
@@ -33,8 +33,9 @@ def split_heads(flat: torch.Tensor, counts: Dict[str, int]) -> Dict[str, torch.T
 
 
 def head_terms(logits: Dict[str, torch.Tensor], actions: Dict[str, torch.Tensor], masks: Dict[str, torch.Tensor],
-               stable: bool = True):
-    """Per head: log-probs, selected log-prob (B,S), selection count, entropy-sum."""
+               stable: bool = True, step_weight: Optional[torch.Tensor] = None):
+    """Per head: log-probs, selected log-prob (B,S), selection count, entropy-sum. ``step_weight`` (B,S) or (B,1)
+    multiplies every step's entropy inside the sum (the selection counts stay unweighted)."""
     out = {}
     for key, lg in logits.items():
         m = masks[key].bool()
@@ -43,7 +44,10 @@ def head_terms(logits: Dict[str, torch.Tensor], actions: Dict[str, torch.Tensor]
         sel_logp = (logp * a).sum(-1)                     # (B,S): log-prob of the chosen entry (0 if none)
         n_sel = a.sum()
         p = torch.exp(logp) * m
-        ent_sum = -(p * torch.where(m, logp, torch.zeros_like(logp))).sum()
+        plogp = p * torch.where(m, logp, torch.zeros_like(logp))
+        if step_weight is not None:
+            plogp = plogp * step_weight.to(plogp.dtype).unsqueeze(-1)
+        ent_sum = -plogp.sum()
         out[key] = (logp, sel_logp, n_sel, ent_sum)
     return out
 
@@ -83,28 +87,36 @@ def vpg_loss(logits: Dict[str, torch.Tensor], values: torch.Tensor, actions: Dic
 def ppo_loss(logits: Dict[str, torch.Tensor], values: torch.Tensor, actions: Dict[str, torch.Tensor],
              masks: Dict[str, torch.Tensor], advantages: torch.Tensor, returns: torch.Tensor,
              logp_old: torch.Tensor, clip_eps: float, entropy_coef: float, vf_coef: float, stable: bool = True,
-             offpolicy: str = 'clip'):
+             offpolicy: str = 'clip', seq_weight: Optional[torch.Tensor] = None):
     """Clipped-surrogate PPO on the joint (summed over sampled heads) log-probability. All per-step tensors (B,S).
+
+    ``seq_weight`` (B,): per-sequence loss weights (the importance-sampling weights of a prioritised replay,
+    ops/replay.py), broadcast over the sequence's steps: they multiply every step's policy term, squared value error
+    and entropy; the normalisers (valid steps, selections per head) and the diagnostics stay unweighted.
 
     ``offpolicy='tis'``: the policy term is the off-policy policy gradient with the truncated importance weight
     w = min(1, π/π_old) held constant (V-trace style, for replayed experience): value −mean(w·A), gradient
     −mean(w·A·∇log π); ``clipfrac`` then counts the truncated rows (π > π_old)."""
-    terms = head_terms(logits, actions, masks, stable=stable)
+    sw = None
+    if seq_weight is not None:
+        sw = seq_weight.reshape(-1, 1).to(values.dtype)     # (B,1) over (B,S)
+    terms = head_terms(logits, actions, masks, stable=stable, step_weight=sw)
     logp = sum(t[1] for t in terms.values())
     valid = sum(actions[k].sum(-1) for k in actions).gt(0).to(logp.dtype)   # padded steps select nothing
     n_valid = valid.sum().clamp_min(1.0)
+    wvalid = valid if sw is None else valid * sw            # the loss terms' row weights
     log_ratio = logp - logp_old
     ratio = torch.exp(log_ratio)
     if offpolicy == 'tis':
         w = ratio.detach().clamp(max=1.0)
-        policy_loss = -(w * advantages * (1.0 + logp - logp.detach()) * valid).sum() / n_valid
+        policy_loss = -(w * advantages * (1.0 + logp - logp.detach()) * wvalid).sum() / n_valid
     else:
         surr1 = ratio * advantages
         surr2 = torch.clamp(ratio, 1.0 - clip_eps, 1.0 + clip_eps) * advantages
-        policy_loss = -(torch.minimum(surr1, surr2) * valid).sum() / n_valid
+        policy_loss = -(torch.minimum(surr1, surr2) * wvalid).sum() / n_valid
     v = values.squeeze(-1)
     if vf_coef > 0:
-        value_loss = vf_coef * ((v - returns).pow(2) * valid).sum() / n_valid
+        value_loss = vf_coef * ((v - returns).pow(2) * wvalid).sum() / n_valid
     else:   # keep the value head out of the graph (reference sparse-param semantics, optimizer.py:667-670)
         value_loss = torch.zeros((), device=v.device, dtype=v.dtype)
     ents = _entropies(terms)

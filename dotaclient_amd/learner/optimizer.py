@@ -88,6 +88,11 @@ class OptimizerConfig:
     replay_priority_alpha: float = 0.6
     replay_priority_eta: float = 0.9
     replay_priority_eps: float = 1e-3
+    # importance-sampling weights of the mixture sampler: w = (N·q)^(−beta) / max over the minibatch on every sampled
+    # sequence's loss (0 = off: the sampler's bias stays uncorrected); beta_anneal = N: linear from beta to 1 over N
+    # iterations (0 = constant)
+    replay_priority_beta: float = 0.0
+    replay_priority_beta_anneal: int = 0
     # replay steps per iteration = ratio × epochs × (fresh sequences // batch_size), the fractional remainder carried
     # to the next iteration (at least one step per iteration); 1.0 = as often as fresh data arrives
     replay_ratio: float = 1.0
@@ -223,6 +228,15 @@ class DotaOptimizer:
             raise ValueError("replay_sampler='mixture' with replay_priority_alpha > 0 takes its priorities from the "
                              "in-step V-trace advantages: it needs advantages='vtrace-step' (on the device ingest) and "
                              f"algo='ppo' (got advantages={cfg.advantages!r}, algo={cfg.algo!r}, ingest {dev_ingest})")
+        if cfg.replay_priority_beta > 0 and cfg.replay_sampler != 'mixture':
+            raise ValueError("replay_priority_beta > 0 weights the draws of the prioritised sampler: it needs "
+                             f"replay_sampler='mixture' (got {cfg.replay_sampler!r}; the uniform sampler has no bias "
+                             "to correct)")
+        if cfg.replay_priority_beta > 0 and cfg.algo != 'ppo':
+            raise ValueError("replay_priority_beta > 0 needs algo='ppo': the VPG loss has no per-sequence weights "
+                             f"(got algo={cfg.algo!r})")
+        if not 0.0 <= cfg.replay_priority_beta <= 1.0 or cfg.replay_priority_beta_anneal < 0:
+            raise ValueError('replay_priority_beta must lie in [0, 1] and replay_priority_beta_anneal be >= 0')
         self._replay_carry = 0.0           # fractional replay steps owed to the next iteration (replay_ratio)
         lc = LossConfig(algo=cfg.algo, learning_rate=cfg.learning_rate, entropy_coef=cfg.entropy_coef,
                         vf_coef=cfg.vf_coef, clip_eps=cfg.clip_eps, gamma=cfg.gamma, gae_lambda=cfg.gae_lambda,
@@ -293,7 +307,8 @@ class DotaOptimizer:
                                                                        vtrace=self.vtrace_step, prioritized=prio)
             kw = dict(prioritized=True, sampler='mixture', recent_frac=cfg.replay_recent_frac,
                       priority_alpha=cfg.replay_priority_alpha, priority_eta=cfg.replay_priority_eta,
-                      priority_eps=cfg.replay_priority_eps) if prio else {}
+                      priority_eps=cfg.replay_priority_eps, priority_beta=cfg.replay_priority_beta,
+                      priority_beta_anneal=cfg.replay_priority_beta_anneal) if prio else {}
             self.replay = HbmReplay(cap, cfg.seq_len, self.policy_cfg.layout, hid, self.device, seed=cfg.seed,
                                     reset=pk, vtrace=self.vtrace_step, **kw)
             logger.info('on-device replay: %d sequences, %.2f GB', cap, self.replay.nbytes / 1e9)
@@ -853,6 +868,9 @@ class DotaOptimizer:
             self.replay.add(data, version=it)
             if cfg.replay_prefill and self.replay.fill_fraction < 1.0:
                 self.replay.prefill()
+            weighted = getattr(self.replay, 'weighted', False)
+            if weighted:
+                self.replay.set_iteration(it - 1)       # the annealed importance-sampling exponent of this iteration
             n_replay = cfg.epochs * (n // cfg.batch_size)
             if cfg.replay_ratio != 1.0:
                 # replay_ratio × the fresh-data count, the fraction carried over so the long-run ratio is exact
@@ -867,6 +885,8 @@ class DotaOptimizer:
             if getattr(self.replay, 'prioritized', False):
                 # (one value per iteration: the running count of non-finite priorities)
                 metrics_acc['replay/priority_nonfinite'] = [self.replay.priority_nonfinite.clone()]
+            if weighted:
+                metrics_acc['replay/beta'] = [torch.full((), self.replay.beta, device=self.device)]
         pool = self._iteration_pool(data, n) if (self.replay is None and self.learner.direct()) else None
         for ep in range(cfg.epochs if self.replay is None else 0):
             perm = torch.randperm(n, generator=g)
@@ -1122,6 +1142,13 @@ class DotaOptimizer:
                 metrics['replay/sample_age'] = mean['replay/age_sum'] / B
                 metrics['replay/recent_draw_frac'] = mean['replay/recent_draws'] / B
                 metrics['replay/priority_nonfinite'] = mean['replay/priority_nonfinite']
+            if 'replay/is_weight_sum' in mean:
+                # importance-sampling weights: mean over all draws, the minibatch minimum averaged over the steps,
+                # and the draws per step that no branch of the mixture could have made (clamped fall-backs)
+                metrics['replay/is_weight_mean'] = mean['replay/is_weight_sum'] / float(cfg.batch_size)
+                metrics['replay/is_weight_min'] = mean['replay/is_weight_min']
+                metrics['replay/beta'] = mean['replay/beta']
+                metrics['replay/zero_prob_draws'] = mean['replay/zero_prob_draws']
             if 'replay/priority_sum' in mean or cfg.replay_ratio != 1.0:
                 metrics['replay/ratio'] = p['n_train'] / max(1, p.get('n_fresh', 0))
         for team, v in self.running.mean.items():

@@ -15,10 +15,14 @@ Sampling is uniform over the filled part, optionally restricted to the ``recent`
 ``recent_frac`` of the draws uniform over the ``recent`` newest sequences, the rest proportional to a per-sequence
 priority over the whole ring. The priority ``(eta·max|A| + (1 − eta)·mean|A| + eps)^alpha`` comes from the in-step
 V-trace advantages of the step that last trained on the sequence (``update_priorities``); new sequences enter at the
-current maximum. Sampler, priorities and their statistics live on the replay's device: no host sync per step. Off-policy
-correction: the PPO ratio against the stored behaviour ``logp_old``, and — with the in-step V-trace (``vtrace``,
-learner/optimizer.py advantages='vtrace-step') — every sampled sequence's advantages and value targets recomputed
-at the weights being trained, with truncated importance weights against that behaviour log-prob.
+current maximum. ``priority_beta`` > 0 adds the importance-sampling correction of prioritised replay: every draw's
+weight ``(size·q)^(−beta) / max`` over the minibatch (ops/replay.py), written by the same sampling pass into a fixed
+buffer (``seq_weight``) that the learner step multiplies into the sequence's policy, value and entropy terms;
+``priority_beta_anneal`` = N moves beta linearly to 1 over N iterations (``set_iteration``). The priorities themselves
+never see the weights. Sampler, priorities and their statistics live on the replay's device: no host sync per step.
+Off-policy correction: the PPO ratio against the stored behaviour ``logp_old``, and — with the in-step V-trace
+(``vtrace``, learner/optimizer.py advantages='vtrace-step') — every sampled sequence's advantages and value targets
+recomputed at the weights being trained, with truncated importance weights against that behaviour log-prob.
 """
 from __future__ import annotations
 
@@ -65,7 +69,7 @@ class HbmReplay:
     def __init__(self, capacity: int, S: int, layout: UnitLayout, hidden: Optional[int], device, seed: int = 0,
                  reset: bool = False, vtrace: bool = False, prioritized: bool = False, sampler: str = 'uniform',
                  recent_frac: float = 0.5, priority_alpha: float = 0.6, priority_eta: float = 0.9,
-                 priority_eps: float = 1e-3):
+                 priority_eps: float = 1e-3, priority_beta: float = 0.0, priority_beta_anneal: int = 0):
         if capacity < 1:
             raise ValueError('replay capacity must be >= 1')
         if sampler not in ('uniform', 'mixture'):
@@ -76,6 +80,12 @@ class HbmReplay:
             raise ValueError(f'recent_frac must lie in [0, 1], got {recent_frac}')
         if priority_alpha < 0 or not 0.0 <= priority_eta <= 1.0 or priority_eps <= 0:
             raise ValueError('priority_alpha >= 0, 0 <= priority_eta <= 1 and priority_eps > 0 are required')
+        if not 0.0 <= priority_beta <= 1.0 or priority_beta_anneal < 0:
+            raise ValueError(f'priority_beta must lie in [0, 1] and priority_beta_anneal be >= 0, got {priority_beta}, '
+                             f'{priority_beta_anneal}')
+        if priority_beta > 0 and sampler != 'mixture':
+            raise ValueError("priority_beta > 0 (importance-sampling weights) needs sampler='mixture': the uniform "
+                             "sampler draws without bias and has no weights")
         self.capacity = int(capacity)
         self.S = S
         self.device = torch.device(device)
@@ -97,6 +107,11 @@ class HbmReplay:
         self.priority_alpha, self.priority_eta = float(priority_alpha), float(priority_eta)
         self.priority_eps = float(priority_eps)
         self.current_version = 0        # newest version added: the sampler's age statistic counts from it
+        # importance-sampling weights: off at beta = 0 (nothing about sampling or the step changes), else for good —
+        # an annealed beta moves, the switch does not, so a captured step stays wired to the weight buffer
+        self.priority_beta0, self.priority_beta_anneal = float(priority_beta), int(priority_beta_anneal)
+        self.beta = self.priority_beta0
+        self.weighted = self.priority_beta0 > 0
         if self.prioritized:
             from ..ops.replay import SamplerState
             # one fp32 priority per slot (0 = unfilled): a separate attribute, not a field the learner step gathers
@@ -222,6 +237,24 @@ class HbmReplay:
         ev.record()
         return out
 
+    def set_iteration(self, iteration: int) -> float:
+        """The importance-sampling exponent of learner iteration ``iteration`` (0-based): constant, or linear from
+        ``priority_beta`` to 1 over ``priority_beta_anneal`` iterations. Returns it."""
+        if self.weighted and self.priority_beta_anneal > 0:
+            t = min(1.0, max(0.0, iteration / self.priority_beta_anneal))
+            self.beta = self.priority_beta0 + (1.0 - self.priority_beta0) * t
+        return self.beta
+
+    def seq_weight(self, B: int) -> Optional[torch.Tensor]:
+        """The last sampling pass's importance weights of a ``B``-sequence minibatch: a view at a fixed address of the
+        sampler state's buffer (what a captured step is wired to); None when the weights are off."""
+        if not self.weighted:
+            return None
+        w = self.sampler_state.is_weight
+        if B > w.numel():
+            raise ValueError(f'importance-sampling weights: at most {w.numel()} sequences per minibatch (got {B})')
+        return w[:B]
+
     def _sample_mixture(self, out: torch.Tensor, recent: Optional[int] = None, u_out=None) -> torch.Tensor:
         """The mixture sampler (ops/replay.py) into ``out`` (int64 on the replay's device — a captured step's static
         index buffer, or a fresh tensor): on the GPU two launches reading the priorities where they are, the draw
@@ -229,9 +262,12 @@ class HbmReplay:
         pass's maximum priority and statistics in ``sampler_state``."""
         from ..ops import replay as R
         st = self.sampler_state
+        w_out = self.seq_weight(out.numel())
         if self.device.type == 'cuda':
             return R.sample_mixture(self.priority, self.version, st, out, self.size, self.cursor, recent,
-                                    self.recent_frac, self.current_version, u_out)
+                                    self.recent_frac, self.current_version, u_out,
+                                    beta=self.beta if self.weighted else 0.0,
+                                    w_out=st.is_weight if self.weighted else None)
         u = torch.rand(out.numel(), 2, generator=self._g)
         if u_out is not None:
             u_out.copy_(u)
@@ -241,6 +277,11 @@ class HbmReplay:
         st.stats[:3].copy_(stats)
         st.stats[3] = float(st.max_priority)
         st.counter += 1
+        if w_out is not None:
+            w, ws = R.importance_weights_reference(self.priority, idx, self.size, self.cursor, self.capacity, recent,
+                                                   self.recent_frac, self.beta)
+            w_out.copy_(w)
+            st.stats[R.N_STATS:R.N_STATS + R.N_STATS_IS].copy_(ws)
         return out.copy_(idx)
 
     def update_priorities(self, idx: torch.Tensor, pf: torch.Tensor):

@@ -282,13 +282,18 @@ def _forward(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], units_t
 def _heads_loss(fp, W: Dict[str, torch.Tensor], f: Forward, act_t, msk_t, adv_t, ret_t, lpo_t, nret_t, norms,
                 B: int, S: int, vt_t: Optional[torch.Tensor]) -> Heads:
     """The heads / loss kernel (loss partials, log-probs, ∂z, ∂pointer logits) and ∂h = ∂z·W_cat, preceded by the
-    in-step V-trace when ``vt_t`` is given. Sets ``fp.vtrace_stats``."""
+    in-step V-trace when ``vt_t`` is given. Sets ``fp.vtrace_stats``. ``fp.seq_weight`` ((B,) f32 at a fixed address:
+    the importance weights of a prioritised replay's sampling pass, learner/engine.py) weights the sequences' loss
+    terms in the loss call; the forward-only V-trace call and the priorities never see it."""
     C, lc = fp.C, fp.loss_cfg
     exact = fp.exact
     N, H = B * S, fp.cfg.hidden
     # heads_loss algo: 0 = PPO clipped surrogate, 1 = VPG (reference), 2 = PPO's truncated-IS off-policy term
     algo = (2 if getattr(lc, 'offpolicy', 'clip') == 'tis' else 0) if lc.algo == 'ppo' else 1
     fp.vtrace_stats = None
+    sw = getattr(fp, 'seq_weight', None)
+    if sw is not None and (algo == 1 or sw.numel() != B):
+        raise ValueError('per-sequence loss weights: one weight per sequence, PPO objectives only (not the VPG loss)')
     if vt_t is not None:
         # V-trace INSIDE the step (LossConfig.vtrace): this step's own values (z column 149) and log-probs of the
         # recorded actions (a first, forward-only pass of the heads kernel) against the actor's behaviour
@@ -312,7 +317,7 @@ def _heads_loss(fp, W: Dict[str, torch.Tensor], f: Forward, act_t, msk_t, adv_t,
         C.adv_normalize(adv_v, vt_t[:, 2].contiguous(), adv_t, float(EPS))
     dz, dtl, part, logp = C.heads_loss(f.z, f.emb, act_t, msk_t, adv_t, ret_t, lpo_t, nret_t, norms, algo,
                                        bool(lc.compat_value_bug), S, B, float(lc.clip_eps), float(lc.entropy_coef),
-                                       float(lc.vf_coef), dz_bf16=False, precise=exact)
+                                       float(lc.vf_coef), dz_bf16=False, precise=exact, seq_weight=sw)
     dxh = C.rowmm_in256(dz, *W['heads_wT']).view(S, B, H)
     return Heads(part, logp, dz, dtl, dxh)
 

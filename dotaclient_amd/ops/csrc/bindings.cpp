@@ -331,7 +331,8 @@ std::vector<torch::Tensor> heads_loss(torch::Tensor z, torch::Tensor emb, torch:
                                       torch::Tensor adv, torch::Tensor ret, torch::Tensor logp_old,
                                       torch::Tensor nret, torch::Tensor norms, int64_t algo, bool compat_value_bug,
                                       int64_t S_bug, int64_t B_bug, double clip_eps, double ent_coef,
-                                      double vf_coef, bool dz_bf16, bool precise) {
+                                      double vf_coef, bool dz_bf16, bool precise,
+                                      c10::optional<torch::Tensor> seq_weight) {
   CHECK_F32(z); CHECK_DEV(emb); CHECK_CONTIG(emb); CHECK_U8(act); CHECK_U8(msk); CHECK_F32(adv); CHECK_F32(ret);
   CHECK_F32(logp_old); CHECK_F32(nret); CHECK_F32(norms);
   const bool ef32 = emb.scalar_type() == at::kFloat;
@@ -343,6 +344,16 @@ std::vector<torch::Tensor> heads_loss(torch::Tensor z, torch::Tensor emb, torch:
   TORCH_CHECK(adv.numel() == N && ret.numel() == N && logp_old.numel() == N && nret.numel() == N, "per-row inputs");
   TORCH_CHECK(norms.numel() >= 8, "norms must hold 8 floats");
   TORCH_CHECK(ldz % 4 == 0 && ldz >= 150 && U <= 64, "ldz must be a multiple of 4 and >= 150; U <= 64");
+  // seq_weight (B) f32: per-sequence loss weights over time-major rows (row n → sequence n % B), PPO-family only
+  const float* seqw = nullptr;
+  int Bw = 0;
+  if (seq_weight.has_value() && seq_weight->defined()) {
+    CHECK_F32((*seq_weight));
+    Bw = (int)seq_weight->numel();
+    TORCH_CHECK(algo != 1, "heads_loss: per-sequence loss weights are not defined for the VPG objective");
+    TORCH_CHECK(Bw >= 1 && N % Bw == 0, "heads_loss: seq_weight must hold one weight per sequence (N = S·B rows)");
+    seqw = ptr<float>(*seq_weight);
+  }
   auto dz = dz_bf16 ? torch::empty_like(z, z.options().dtype(at::kBFloat16)) : torch::empty_like(z);
   auto dtl = torch::empty({N, U}, z.options());
   const int nb = dca_heads_loss_nblocks(N);
@@ -353,7 +364,7 @@ std::vector<torch::Tensor> heads_loss(torch::Tensor z, torch::Tensor emb, torch:
                            ptr<float>(norms), dz_bf16 ? nullptr : ptr<float>(dz), ptr<float>(dtl), ptr<float>(part),
                            ptr<float>(logp), N, U, (int)algo, compat_value_bug ? 1 : 0, (int)S_bug, (int)B_bug,
                            (float)clip_eps, (float)ent_coef, (float)vf_coef, cur_stream(),
-                           dz_bf16 ? ptr<short>(dz) : nullptr, ef32 ? 1 : 0, precise && ef32 ? 1 : 0),
+                           dz_bf16 ? ptr<short>(dz) : nullptr, ef32 ? 1 : 0, precise && ef32 ? 1 : 0, seqw, Bw),
             "dca_heads_loss");
   return {dz, dtl, part, logp};
 }
@@ -1208,10 +1219,12 @@ std::vector<torch::Tensor> replay_gather(std::vector<torch::Tensor> pools, int64
 // Prioritised mixture sampler (replay_sample.hip): priority (capacity) f32, version (capacity) i64, the sampler's
 // device state (block sums / maxima, draw counter), out (B) i64 = the caller's index buffer; writes max_priority (1),
 // stats (4) f64 {newest-window draws, Σ version lag, Σ P[idx], max P} and, if given, the uniforms u_out (B, 2).
+// With w_out (≥ B) f32 also the draws' importance-sampling weights (size·q)^(−beta) / their maximum, and stats (7)
+// gains {Σ w, min w, draws with q = 0}.
 void replay_sample(torch::Tensor priority, torch::Tensor version, torch::Tensor block_sum, torch::Tensor block_max,
                    torch::Tensor counter, int64_t seed, torch::Tensor out, torch::Tensor max_priority,
                    torch::Tensor stats, c10::optional<torch::Tensor> u_out, int64_t size, int64_t cursor, int64_t m,
-                   double recent_frac, int64_t current_version) {
+                   double recent_frac, int64_t current_version, double beta, c10::optional<torch::Tensor> w_out) {
   CHECK_F32(priority); CHECK_F32(block_max); CHECK_F32(max_priority);
   CHECK_DEV(version); CHECK_CONTIG(version); CHECK_DT(version, at::kLong);
   CHECK_DEV(counter); CHECK_CONTIG(counter); CHECK_DT(counter, at::kLong);
@@ -1233,11 +1246,19 @@ void replay_sample(torch::Tensor priority, torch::Tensor version, torch::Tensor 
     TORCH_CHECK(u_out->numel() == 2 * B, "replay_sample: u_out must be (B, 2)");
     u = ptr<float>(*u_out);
   }
+  float* wo = nullptr;
+  if (w_out.has_value() && w_out->defined()) {
+    CHECK_F32((*w_out));
+    TORCH_CHECK(w_out->numel() >= B, "replay_sample: w_out must hold one weight per draw");
+    TORCH_CHECK(stats.numel() >= 7, "replay_sample: importance weights need 7 statistics");
+    TORCH_CHECK(beta >= 0.0, "replay_sample: beta must be >= 0");
+    wo = ptr<float>(*w_out);
+  }
   hip_check(dca_replay_sample(ptr<float>(priority), ptr<long long>(version), ptr<double>(block_sum),
                               ptr<float>(block_max), (int)cap, (int)size, (int)cursor, (int)m, (float)recent_frac,
                               (long long)current_version, (unsigned long long)seed, ptr<long long>(counter),
                               ptr<long long>(out), (int)B, ptr<float>(max_priority), ptr<double>(stats), u,
-                              cur_stream()), "dca_replay_sample");
+                              cur_stream(), beta, wo), "dca_replay_sample");
 }
 
 // Per-sequence priorities of a time-major minibatch (replay_sample.hip seq_priority_kernel): adv (B·S), vt (B·S, 4),
@@ -1281,7 +1302,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("z"), py::arg("emb"), py::arg("act"), py::arg("msk"), py::arg("adv"), py::arg("ret"),
         py::arg("logp_old"), py::arg("nret"), py::arg("norms"), py::arg("algo"), py::arg("compat_value_bug"),
         py::arg("S_bug"), py::arg("B_bug"), py::arg("clip_eps"), py::arg("ent_coef"), py::arg("vf_coef"),
-        py::arg("dz_bf16") = false, py::arg("precise") = false);
+        py::arg("dz_bf16") = false, py::arg("precise") = false, py::arg("seq_weight") = py::none());
   m.def("encoder_fwd", &encoder_fwd, "fused entity encoder forward (unit MLP, per-type GEMM, max-pool+argmax)",
         py::arg("units"), py::arg("env"), py::arg("w1"), py::arg("b1"), py::arg("wt"), py::arg("bt"), py::arg("we"),
         py::arg("be"), py::arg("counts"), py::arg("compat"), py::arg("exact") = false,
@@ -1370,7 +1391,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "[K/32][R][32] images, the dpre_dx operand layout)", py::arg("src"), py::arg("slab_major") = false);
   m.def("enc_small_grads", &enc_small_grads, "entity-encoder type-bias and env-layer gradients in one pass");
   m.def("replay_gather", &replay_gather, "minibatch gather from an HBM replay pool into time-major rows (one launch)");
-  m.def("replay_sample", &replay_sample, "prioritised mixture sampler over the replay ring (two launches, no sync)");
+  m.def("replay_sample", &replay_sample, "prioritised mixture sampler over the replay ring (two launches, no sync)",
+        py::arg("priority"), py::arg("version"), py::arg("block_sum"), py::arg("block_max"), py::arg("counter"),
+        py::arg("seed"), py::arg("out"), py::arg("max_priority"), py::arg("stats"), py::arg("u_out"), py::arg("size"),
+        py::arg("cursor"), py::arg("m"), py::arg("recent_frac"), py::arg("current_version"), py::arg("beta") = 0.0,
+        py::arg("w_out") = py::none());
   m.def("seq_priority", &seq_priority, "per-sequence priorities (P, non-finite flag) from a step's advantages");
   m.def("priority_scatter", &priority_scatter, "priority[idx] = P of the step's sequences + non-finite counter");
   m.def("vtrace_step", &vtrace_step, "V-trace advantages / value targets of a minibatch from the step's own values",

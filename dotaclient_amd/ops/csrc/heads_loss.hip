@@ -16,6 +16,12 @@
 //   norms[0] = 1/n_valid  norms[1] = 1/total_selections  norms[2..5] = 1/n_sel[head] (0 if none)
 //   norms[6] = Σ G_last (VPG compat value-bug term)
 //
+// seqw (B floats, optional): per-sequence loss weights of a prioritised replay's minibatch (importance-sampling
+// weights, replay_sample.hip). Rows are time-major, so row n belongs to sequence n % B; its weight multiplies the
+// row's policy, value and entropy terms and their gradients (PPO-family objectives). The normalisers and the
+// diagnostic sums (part[6], [7], [8], [11]) stay unweighted. Without seqw the weight is the constant 1: the products
+// are exact, the outputs bit-identical.
+//
 // emb is the kernel's HBM traffic (229 MB of fp32 at N = 11 200, U = 40: it ran at HBM speed loading all of it), and
 // most of it cannot reach the result: only units with a target-head mask or action byte set are loaded (on the
 // learner's 1v1 experience 11 % of the (row, unit) pairs, two thirds of the rows none) — see `need` below.
@@ -37,6 +43,7 @@ struct Params {
   short* dz16;   // if set: ∂L/∂z written in bf16 here instead of f32 to dz (what the backward GEMMs consume)
   int N, U, algo, compat_value_bug, S_bug, B_bug;
   float clip_eps, ent_coef, vf_coef;
+  const float* seqw; int B;
 };
 
 __device__ __forceinline__ void put_dz(const Params& P, size_t i, float v) {
@@ -97,6 +104,8 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(Params P) {
     }
     const float zl = zr[kQ + min(lane, 21)];                 // enum | x | y logits and the value
     const float A_n = P.adv[n], R_n = P.ret[n], lpo_n = P.logp_old[n], nret_n = P.nret[n];
+    // the sequence's loss weight: one value per wave (n is wave-uniform), so it lives in a scalar register
+    const float w_n = P.seqw ? P.seqw[__builtin_amdgcn_readfirstlane(n) % P.B] : 1.f;
     float nm[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) nm[i] = P.norms[i];
@@ -179,7 +188,7 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(Params P) {
       const int ns = __popcll(__ballot(a[h] > 0.f));
       nsel += ns;
       // entropy of this head over valid entries: -Σ m p logp
-      acc[2 + h] += -dca::wave_sum(mk[h] ? pr[h] * logp[h] : 0.f);
+      acc[2 + h] += w_n * -dca::wave_sum(mk[h] ? pr[h] * logp[h] : 0.f);
     }
     const float valid = nsel > 0 ? 1.f : 0.f;
     const float V = s_zl[wv][21];
@@ -192,11 +201,11 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(Params P) {
       const float s1 = r * A;
       const float rc = fminf(fmaxf(r, 1.f - P.clip_eps), 1.f + P.clip_eps);
       const float s2 = rc * A;
-      acc[0] += valid * fminf(s1, s2);
+      acc[0] += w_n * (valid * fminf(s1, s2));
       const bool clipped = (A > 0.f && r > 1.f + P.clip_eps) || (A < 0.f && r < 1.f - P.clip_eps);
-      g_sel = clipped ? 0.f : -valid * A * r * nm[0];
-      acc[1] += valid * (V - R) * (V - R);
-      dV = P.vf_coef * 2.f * (V - R) * valid * nm[0];
+      g_sel = clipped ? 0.f : w_n * (-valid * A * r * nm[0]);
+      acc[1] += w_n * (valid * (V - R) * (V - R));
+      dV = w_n * (P.vf_coef * 2.f * (V - R) * valid * nm[0]);
       acc[6] += valid * (-lr);
       acc[7] += valid * (fabsf(r - 1.f) > P.clip_eps ? 1.f : 0.f);
       acc[8] += valid * A;
@@ -207,10 +216,10 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(Params P) {
       const float lr = sel - lpo_n;
       const float r = xexp<PRECISE>(lr);
       const float w = fminf(r, 1.f);
-      acc[0] += valid * w * A;
-      g_sel = -valid * A * w * nm[0];
-      acc[1] += valid * (V - R) * (V - R);
-      dV = P.vf_coef * 2.f * (V - R) * valid * nm[0];
+      acc[0] += w_n * (valid * w * A);
+      g_sel = w_n * (-valid * A * w * nm[0]);
+      acc[1] += w_n * (valid * (V - R) * (V - R));
+      dV = w_n * (P.vf_coef * 2.f * (V - R) * valid * nm[0]);
       acc[6] += valid * (-lr);
       acc[7] += valid * (r > 1.f ? 1.f : 0.f);
       acc[8] += valid * A;
@@ -238,7 +247,8 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(Params P) {
     for (int h = 0; h < 4; ++h) {
       const bool in = lane < hw[h];
       float dlp = g_sel * a[h];
-      if (P.ent_coef > 0.f) dlp += P.ent_coef * nm[2 + h] * (mk[h] ? pr[h] * (1.f + logp[h]) : 0.f);
+      // (w_n on the coefficient: the last product still contracts with the sum as it does without weights)
+      if (P.ent_coef > 0.f) dlp += w_n * P.ent_coef * nm[2 + h] * (mk[h] ? pr[h] * (1.f + logp[h]) : 0.f);
       if (!in) dlp = 0.f;
       const float sd = dca::wave_sum(dlp);
       const float dl = dlp - (mk[h] ? pr[h] : 0.f) * sd;
@@ -308,10 +318,13 @@ extern "C" hipError_t dca_heads_loss(const float* z, int ldz, const void* emb, c
                                      const float* logp_old, const float* nret, const float* norms, float* dz,
                                      float* dtl, float* part, float* logp_out, int N, int U, int algo,
                                      int compat_value_bug, int S_bug, int B_bug, float clip_eps, float ent_coef,
-                                     float vf_coef, hipStream_t st, short* dz16, int emb_f32, int precise) {
+                                     float vf_coef, hipStream_t st, short* dz16, int emb_f32, int precise,
+                                     const float* seqw, int B) {
   if (U > 64 || U < 1 || ldz < kQ + 22 || A != 21 + U) return hipErrorInvalidValue;
+  // weights: PPO-family objectives only, and whole time steps of B sequences
+  if (seqw && (algo == 1 || B < 1 || N % B != 0)) return hipErrorInvalidValue;
   Params P{z, ldz, emb, act, msk, A, adv, ret, logp_old, nret, norms, dz, dtl, part, logp_out, dz16, N, U, algo,
-           compat_value_bug, S_bug, B_bug, clip_eps, ent_coef, vf_coef};
+           compat_value_bug, S_bug, B_bug, clip_eps, ent_coef, vf_coef, seqw, B};
   if (emb_f32 && precise) heads_loss_kernel<true, true><<<dca_heads_loss_nblocks(N), 256, 0, st>>>(P);
   else if (emb_f32) heads_loss_kernel<true, false><<<dca_heads_loss_nblocks(N), 256, 0, st>>>(P);
   else heads_loss_kernel<false, false><<<dca_heads_loss_nblocks(N), 256, 0, st>>>(P);

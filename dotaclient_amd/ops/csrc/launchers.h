@@ -58,7 +58,8 @@ hipError_t dca_heads_loss(const float* z, int ldz, const void* emb, const unsign
                           int A, const float* adv, const float* ret, const float* logp_old, const float* nret,
                           const float* norms, float* dz, float* dtl, float* part, float* logp_out, int N, int U,
                           int algo, int compat_value_bug, int S_bug, int B_bug, float clip_eps, float ent_coef,
-                          float vf_coef, hipStream_t st, short* dz16, int emb_f32, int precise = 0);
+                          float vf_coef, hipStream_t st, short* dz16, int emb_f32, int precise = 0,
+                          const float* seqw = nullptr, int B = 0);   // seqw: per-sequence loss weights, row n → n % B
 
 hipError_t dca_encoder_fwd(const float* units, const float* env, const float* w1, const float* b1, const void* wt,
                            const float* bt, const float* we, const float* be, void* x896, void* emb,
@@ -145,7 +146,8 @@ hipError_t dca_replay_gather(const void* const* src, void* const* dst, const lon
 hipError_t dca_replay_sample(const float* pri, const long long* version, double* bsum, float* bmax, int capacity,
                              int size, int cursor, int m, float recent_frac, long long cur_version,
                              unsigned long long seed, long long* ctr, long long* idx_out, int B, float* pmax_out,
-                             double* stats, float* u_out, hipStream_t st);
+                             double* stats, float* u_out, hipStream_t st, double beta = 0.0,
+                             float* w_out = nullptr);   // w_out (B): importance weights; then stats holds 7 doubles
 hipError_t dca_seq_priority(const float* adv, const float* vt, float* out, int B, int S, float eta, float alpha,
                             float eps, hipStream_t st);
 hipError_t dca_priority_scatter(float* pri, int capacity, const long long* idx, const float* pf, int B,

@@ -16,6 +16,11 @@
 //      leaves no crossing, the draw takes the block's last slot with P > 0. Writes idx into the caller's buffer (the
 //      captured step's static index buffer), the maximum priority, the next draw counter, the statistics
 //      {newest-window draws, Σ (current version − version[idx]), Σ P[idx], max P} and optionally the uniforms it used.
+//      With `w_out` also every draw's importance-sampling weight: q(idx) = f·[idx in the newest window]/m +
+//      (1 − f)·P[idx]/ΣP is the slot's probability under the whole mixture (whichever branch drew it; ΣP ≤ 0:
+//      [in window]/m), w = (size·q)^(−beta) in double (q = 0, reachable only through the clamped fall-backs: w = 1,
+//      counted), w_out[d] = float(w / max_d w). The maximum goes over the wave partials in LDS, then every wave forms
+//      its draws' weights again and divides; statistics {Σ w_out, min w_out, draws with q = 0} behind the first four.
 //   3. seq_priority_kernel — one workgroup per sequence over the time-major rows r = t·B + b of the step's advantages:
 //      tree reduction of max / sum / count over the valid rows → out[b] = P, out[B + b] = non-finite flag.
 //   4. priority_scatter_kernel — priority[idx[b]] = P[b] (duplicates carry equal values) and the non-finite counter.
@@ -69,6 +74,18 @@ __device__ __forceinline__ void load_run(const float* __restrict__ p, long long 
   }
 }
 
+// un-normalised importance-sampling weight of slot `idx` under the mixture (see the header); `zero` ← (q = 0).
+// No contraction: the float64 oracle (ops/replay.py importance_weights_reference) rounds every operation.
+__device__ __forceinline__ double is_weight_raw(const float* __restrict__ pri, long long idx, int capacity, int size,
+                                                int cursor, int m, double f, double T, double beta, bool& zero) {
+#pragma clang fp contract(off)
+  const long long back = (((long long)cursor - 1 - idx) % capacity + capacity) % capacity;
+  const double win = back < (long long)m ? 1.0 / (double)m : 0.0;
+  const double q = T > 0.0 ? f * win + (1.0 - f) * ((double)pri[idx] / T) : win;
+  zero = !(q > 0.0);
+  return zero ? 1.0 : pow((double)size * q, -beta);
+}
+
 __global__ __launch_bounds__(kT) void priority_block_sums_kernel(const float* __restrict__ pri, int capacity,
                                                                  double* __restrict__ bsum, float* __restrict__ bmax) {
   const long long base = (long long)blockIdx.x * kBlock + (long long)threadIdx.x * kPer;
@@ -102,10 +119,12 @@ __global__ __launch_bounds__(kTS) void replay_sample_kernel(
     const float* __restrict__ pri, const long long* __restrict__ version, const double* __restrict__ bsum,
     const float* __restrict__ bmax, int nblk, int capacity, int size, int cursor, int m, float recent_frac,
     long long cur_version, unsigned long long seed, long long* __restrict__ ctr, long long* __restrict__ idx_out,
-    int B, float* __restrict__ pmax_out, double* __restrict__ stats, float* __restrict__ u_out) {
+    int B, float* __restrict__ pmax_out, double* __restrict__ stats, float* __restrict__ u_out, double beta,
+    float* __restrict__ w_out) {
   __shared__ double pre[kMaxBlocks];          // inclusive prefix sums of the block sums
   __shared__ float smax[kMaxBlocks];
   __shared__ double red[3][kWS];
+  __shared__ double wred[2][kWS];             // importance weights: wave maxima / q = 0 counts, then sums / minima
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if (tid < nblk) {
     pre[tid] = bsum[tid];
@@ -128,6 +147,7 @@ __global__ __launch_bounds__(kTS) void replay_sample_kernel(
   const double T = pre[nblk - 1];
   const bool vec = aligned16(pri);
   double n_new = 0.0, age = 0.0, psum = 0.0;   // this wave's statistics (lane 0 holds them)
+  double wmax = 0.0, nzero = 0.0;
   for (int d = w; d < B; d += kWS) {
     const float u0 = uniform24(seed, c, d, 0), u1 = uniform24(seed, c, d, 1);
     long long idx;
@@ -197,12 +217,19 @@ __global__ __launch_bounds__(kTS) void replay_sample_kernel(
       n_new += newest ? 1.0 : 0.0;
       age += (double)(cur_version - version[idx]);
       psum += (double)pri[idx];
+      if (w_out) {
+        bool zero;
+        wmax = fmax(wmax, is_weight_raw(pri, idx, capacity, size, cursor, m, (double)recent_frac, T, beta, zero));
+        nzero += zero ? 1.0 : 0.0;
+      }
     }
   }
   if (lane == 0) {
     red[0][w] = n_new;
     red[1][w] = age;
     red[2][w] = psum;
+    wred[0][w] = wmax;
+    wred[1][w] = nzero;
   }
   __syncthreads();
   if (tid < 3) {
@@ -211,6 +238,38 @@ __global__ __launch_bounds__(kTS) void replay_sample_kernel(
     stats[tid] = v;
   }
   if (tid == 0) *ctr = (long long)(c + 1);
+  if (w_out) {                                  // (a launch argument: the whole workgroup takes the branch or not)
+    double mx = 0.0, nz = 0.0;
+    for (int k = 0; k < kWS; ++k) {
+      mx = fmax(mx, wred[0][k]);
+      nz += wred[1][k];
+    }
+    __syncthreads();                            // every thread has read the maxima: wred is free again
+    double sw = 0.0, mn = 1.0;
+    if (lane == 0) {
+      for (int d = w; d < B; d += kWS) {        // this wave's own draws again (its lane 0 wrote idx_out[d])
+        bool zero;
+        const float wn =
+            (float)(is_weight_raw(pri, idx_out[d], capacity, size, cursor, m, (double)recent_frac, T, beta, zero) / mx);
+        w_out[d] = wn;
+        sw += (double)wn;
+        mn = fmin(mn, (double)wn);
+      }
+      wred[0][w] = sw;
+      wred[1][w] = mn;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double s = 0.0, lo = 1.0;
+      for (int k = 0; k < kWS; ++k) {
+        s += wred[0][k];
+        lo = fmin(lo, wred[1][k]);
+      }
+      stats[4] = s;
+      stats[5] = lo;
+      stats[6] = nz;
+    }
+  }
 }
 
 __global__ __launch_bounds__(kT) void seq_priority_kernel(const float* __restrict__ adv, const float* __restrict__ vt,
@@ -278,15 +337,15 @@ extern "C" hipError_t dca_replay_sample(const float* pri, const long long* versi
                                         int capacity, int size, int cursor, int m, float recent_frac,
                                         long long cur_version, unsigned long long seed, long long* ctr,
                                         long long* idx_out, int B, float* pmax_out, double* stats, float* u_out,
-                                        hipStream_t st) {
+                                        hipStream_t st, double beta, float* w_out) {
   if (capacity < 1 || capacity > kMaxBlocks * kBlock || B < 1 || size < 1 || size > capacity || m < 1 || m > size ||
-      cursor < 0 || cursor >= capacity)
+      cursor < 0 || cursor >= capacity || (w_out && !(beta >= 0.0)))
     return hipErrorInvalidValue;
   const int nblk = (capacity + kBlock - 1) / kBlock;
   hipLaunchKernelGGL(priority_block_sums_kernel, dim3(nblk), dim3(kT), 0, st, pri, capacity, bsum, bmax);
   DCA_CHECK_LAUNCH();
   hipLaunchKernelGGL(replay_sample_kernel, dim3(1), dim3(kTS), 0, st, pri, version, bsum, bmax, nblk, capacity, size,
-                     cursor, m, recent_frac, cur_version, seed, ctr, idx_out, B, pmax_out, stats, u_out);
+                     cursor, m, recent_frac, cur_version, seed, ctr, idx_out, B, pmax_out, stats, u_out, beta, w_out);
   DCA_CHECK_LAUNCH();
   return hipSuccess;
 }

@@ -17,6 +17,13 @@ Sums are accumulated in double, in a fixed order, so equal (state, seed, counter
 uniforms come from a counter-based hash (the idiom of ``csrc/actor.hip``): the kernel reads the draw counter from device
 memory and writes the next value itself, so a launch changes no host value.
 
+Importance-sampling weights (``beta`` > 0): a slot's probability under the whole mixture, whichever branch drew it, is
+``q(i) = f·[i in the newest window]/m + (1 − f)·P_i/T`` (``f = recent_frac``; ``T ≤ 0``: ``[in window]/m``), its weight
+``w_i = (size·q(i))^(−beta)``, and a minibatch's weights are divided by their maximum, so they lie in (0, 1] and only
+ever scale a sequence's loss down. ``q = 0`` is reachable only through the clamped fall-back paths: such a draw takes
+``w = 1`` before the division and is counted. The sampler kernel writes them next to the indices; the CPU form is
+:func:`importance_weights_reference`.
+
 On a GPU tensor the HIP kernels run (and the extension is required); on CPU the references below run — they are also
 the oracles of the GPU tests.
 """
@@ -30,6 +37,8 @@ import torch
 BLOCK = 4096            # slots per block sum (csrc/replay_sample.hip kBlock)
 MAX_CAPACITY = 1 << 20  # 256 block sums scanned in LDS
 N_STATS = 4             # newest-window draws, Σ (current version − version[idx]), Σ P[idx], max priority
+N_STATS_IS = 3          # behind them, of the importance weights: Σ w, min w, draws with q = 0
+MAX_IS_BATCH = 256      # the largest minibatch of the exact learner: entries of SamplerState.is_weight
 
 
 def priority_from_advantages(adv: torch.Tensor, valid: torch.Tensor, B: int, S: int, eta: float = 0.9,
@@ -77,9 +86,32 @@ def sample_mixture_reference(priority, size: int, cursor: int, capacity: int, re
     return torch.from_numpy(idx), torch.from_numpy(stats)
 
 
+def importance_weights_reference(priority, idx, size: int, cursor: int, capacity: int, recent: Optional[int],
+                                 recent_frac: float, beta: float):
+    """Importance-sampling weights of the drawn slots ``idx`` (B,) in float64 numpy: the oracle of the sampler
+    kernel's ``w_out`` and the CPU replay's own path. Returns (w (B,) float64 tensor, normalised by the batch maximum;
+    stats (3,) float64 tensor = Σ w, min w — both over the weights rounded to float32, as stored — and the draws with
+    q = 0)."""
+    p = np.asarray(torch.as_tensor(priority).detach().cpu().numpy(), dtype=np.float64).reshape(-1)
+    i = np.asarray(torch.as_tensor(idx).detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+    assert p.shape[0] == capacity and 1 <= size <= capacity and beta >= 0
+    m = size if not recent else min(size, int(recent))
+    f = np.float64(np.float32(recent_frac))
+    T = np.cumsum(p)[-1]
+    win = np.where(((cursor - 1 - i) % capacity) < m, 1.0 / np.float64(m), 0.0)
+    q = f * win + (1.0 - f) * (p[i] / T) if T > 0 else win
+    zero = ~(q > 0)
+    w = np.where(zero, 1.0, np.power(np.float64(size) * np.where(zero, 1.0, q), -np.float64(beta)))
+    w = w / w.max()
+    w32 = w.astype(np.float32).astype(np.float64)
+    stats = np.array([w32.sum(), w32.min(), float(zero.sum())], dtype=np.float64)
+    return torch.from_numpy(w), torch.from_numpy(stats)
+
+
 class SamplerState:
     """Device state of one replay's sampler: the draw counter, the block-sum scratch, the maximum priority and the
-    statistics of the last sampling pass. Allocated once; a sampling pass allocates nothing."""
+    statistics of the last sampling pass, and the importance weights of its draws (``is_weight``: a fixed buffer a
+    captured step reads its first ``B`` entries of). Allocated once; a sampling pass allocates nothing."""
 
     def __init__(self, capacity: int, device, seed: int = 0):
         if capacity > MAX_CAPACITY:
@@ -91,20 +123,26 @@ class SamplerState:
         self.block_sum = torch.zeros(nblk, dtype=torch.float64, device=dev)
         self.block_max = torch.zeros(nblk, dtype=torch.float32, device=dev)
         self.max_priority = torch.ones(1, dtype=torch.float32, device=dev)      # 1.0 before any sampling pass
-        self.stats = torch.zeros(N_STATS, dtype=torch.float64, device=dev)
+        self.stats = torch.zeros(N_STATS + N_STATS_IS, dtype=torch.float64, device=dev)
+        self.is_weight = torch.ones(MAX_IS_BATCH, dtype=torch.float32, device=dev)
 
 
 def sample_mixture(priority: torch.Tensor, version: torch.Tensor, state: SamplerState, out: torch.Tensor, size: int,
                    cursor: int, recent: Optional[int], recent_frac: float, current_version: int = 0,
-                   u_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   u_out: Optional[torch.Tensor] = None, beta: float = 0.0,
+                   w_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Draw ``out.numel()`` ring positions into ``out`` (int64, the caller's buffer) on the GPU: two launches
     (``csrc/replay_sample.hip``), no host sync, no allocation. Updates ``state`` (counter, max_priority, stats);
-    ``u_out`` (B, 2) f32 optionally receives the uniforms used."""
+    ``u_out`` (B, 2) f32 optionally receives the uniforms used. With ``w_out`` (≥ B f32, e.g. ``state.is_weight``) the
+    same pass writes the draws' importance-sampling weights at ``beta`` into its first B entries and their statistics
+    into ``state.stats[4:7]``; ``beta`` is a launch argument and may change from pass to pass."""
     from . import require
     m = int(size) if not recent else min(int(size), int(recent))
+    if w_out is None and beta:
+        raise ValueError('sample_mixture: beta > 0 needs w_out, the buffer the weights go to')
     require().replay_sample(priority, version, state.block_sum, state.block_max, state.counter, state.seed, out,
                             state.max_priority, state.stats, u_out, int(size), int(cursor), m, float(recent_frac),
-                            int(current_version))
+                            int(current_version), float(beta), w_out)
     return out
 
 

@@ -1,11 +1,13 @@
 """Cost of the prioritised replay at the bench shape (profiles/replay_prioritized.md): one process = one variant,
 prints one JSON line. Run the step variants interleaved, several times each.
 
-    python scripts/bench_replay_priority.py <variant> [<tree>]     variant: parent | uniform | mixture | kernels
+    python scripts/bench_replay_priority.py <variant> [<tree>]
+    variant: parent | uniform | mixture | mixture_beta | kernels
 
 ``parent`` is ``uniform`` on another source tree (``<tree>``: a checkout of the commit to compare against, with the
-built libraries in place); ``kernels`` times the sampler launches alone (under rocprofv3 --kernel-trace for the
-per-kernel times)."""
+built libraries in place; ``mixture`` with a ``<tree>`` is the mixture sampler on that tree); ``mixture_beta`` adds the
+importance-sampling weights at beta = 0.5 (profiles/replay_is_weights.md); ``kernels`` times the sampler launches alone,
+without and with the weights (under rocprofv3 --kernel-trace for the per-kernel times)."""
 import json
 import os
 import sys
@@ -49,6 +51,11 @@ if variant == 'kernels':
         f = lambda: R.sample_mixture(pri, ver, st, idx, cap, 0, 4096, 0.5)  # noqa: E731
         ev_time(f, 50)
         out[f'sampler_pair_us_cap{cap}'] = [round(1e3 * ev_time(f, 500), 2) for _ in range(5)]
+        if hasattr(st, 'is_weight'):
+            f = lambda: R.sample_mixture(pri, ver, st, idx, cap, 0, 4096, 0.5, beta=0.5,  # noqa: E731
+                                         w_out=st.is_weight)
+            ev_time(f, 50)
+            out[f'sampler_pair_beta_us_cap{cap}'] = [round(1e3 * ev_time(f, 500), 2) for _ in range(5)]
     adv = torch.randn(B * S, device=dev)
     vt = torch.ones(B * S, 4, device=dev)
     o = torch.empty(2, B, device=dev)
@@ -62,7 +69,10 @@ torch.manual_seed(7)
 cfg = get_config('lstm512')
 L = Learner(Policy(cfg), LossConfig(algo='ppo', vtrace=True), device=dev, backend='fused', precision='fp32-exact')
 L.enable_graph(warmup=1)
-kw = dict(prioritized=True, sampler='mixture', recent_frac=0.5) if variant == 'mixture' else {}
+mixture = variant in ('mixture', 'mixture_beta')
+kw = dict(prioritized=True, sampler='mixture', recent_frac=0.5) if mixture else {}
+if variant == 'mixture_beta':
+    kw['priority_beta'] = 0.5
 rep = HbmReplay(CAP, S, cfg.layout, cfg.hidden, dev, seed=0, vtrace=True, **kw)
 rep.host_sampling = True
 b = make_batch(64, S, cfg.layout, cfg.hidden, device=dev, seed=3)
@@ -74,7 +84,7 @@ b['vt'] = torch.stack([torch.randn(64, S, device=dev, generator=g) * 0.3,
                        torch.randn(64, S, device=dev, generator=g) * last, valid, last], -1).contiguous()
 rep.add(b, version=1)
 rep.prefill()
-recent = 4096 if variant == 'mixture' else None
+recent = 4096 if mixture else None
 step = lambda: L.train_step_replay(rep, B, recent)  # noqa: E731
 for _ in range(20):
     m = step()
@@ -87,4 +97,6 @@ for _ in range(3):
     wins.append((round(ms, 4), round(1e3 * (time.perf_counter() - t0) / 100, 4)))
 print(json.dumps({'variant': variant, 'ms_per_step_events': [w[0] for w in wins],
                   'ms_per_step_host': [w[1] for w in wins], 'loss': float(m['loss']), 'graphs': len(L.graphs),
-                  'priority_max': float(rep.priority.max()) if variant == 'mixture' else None}), flush=True)
+                  'priority_max': float(rep.priority.max()) if mixture else None,
+                  'is_weight_min': float(m['replay/is_weight_min']) if variant == 'mixture_beta' else None}),
+      flush=True)
