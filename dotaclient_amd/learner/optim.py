@@ -85,7 +85,7 @@ class FlatAdam:
         if not bool(torch.isfinite(norm)):
             self.nonfinite.fill_(1.0)       # same as the kernels: nothing applied, step counters unchanged
             return norm
-        if self.max_grad_norm is not None:
+        if self.max_grad_norm is not None and self.max_grad_norm > 0:     # None / 0: no clipping, as in the kernel
             coef = (self.max_grad_norm / (norm + 1e-6)).clamp(max=1.0)
             g = g * coef
         active_p = counts > 0
