@@ -20,7 +20,7 @@ Sequence packing (``pack=True``, non-compat): instead of padding every rollout t
 reference, optimizer.py:355-378 — with ≈560-step games in 1400-step sequences 60 % of the trained rows are padding),
 whole rollouts that start from a zero recurrent state are placed first-fit into the free tail of an open sequence.
 The row where such a rollout starts carries a ``reset`` flag: the recurrence treats h, c as zero before that step
-(forward and backward, ops/csrc/lstm_team.hip), so each episode sees exactly the state it would have seen at the start
+(forward and backward, ops/csrc/lstm_team_fwd.hip, lstm_team_bwd.hip), so each episode sees exactly the state it would have seen at the start
 of its own padded sequence. Rollouts longer than a sequence, or starting from a stored non-zero state, keep the
 padded layout (aligned at a sequence start, the stored chunk states as h0 / c0); their last sequence's free tail is
 packed like any other. The return / GAE scan segments are the rollouts in row order.

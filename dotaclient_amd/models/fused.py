@@ -13,7 +13,7 @@ entity encoder     ``encoder.hip``: unit MLP + per-type GEMM + max-pool/argmax; 
                    (5v5: ``attn_block.hip`` LayerNorm + self-attention + out-projection, fwd and bwd)
 pre-RNN + input    ``dx_chain.hip`` forward chain: relu(x896·W_preᵀ + b) then ·W_ihᵀ (or the reference's linear
 projection         fake_rnn layer, policy.py:67-68) in one kernel; backward: the ∂X chain
-recurrence         ``lstm_team.hip``: XCD-team persistent LSTM forward / backward
+recurrence         ``lstm_team_fwd.hip`` / ``lstm_team_bwd.hip``: XCD-team persistent LSTM forward / backward
 heads + loss       ``dx_chain.hip`` heads GEMM + ``heads_loss.hip`` (pointer logits, 4 masked log-softmaxes,
                    PPO/VPG, entropy, value, ∂L/∂every head input)
 weight gradients   ``gemm_tn.hip`` split-K TN GEMM over the B·S rows; ``glue.hip`` small encoder gradients

@@ -490,7 +490,7 @@ def fused_step_tm(fp, W: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor], un
     Returns (partials (R,16) f32, logp (N) f32 time-major, grads {param name → tensor})."""
     assert fp.fp32, 'the fused step runs at fp32 / fp32-exact (bf16: torch backend)'
     if fp.exact and fp.cfg.rnn == 'lstm':
-        # lstm_team.hip plan_exact(): the sequences run as chains of ≤ 8 rows (one XCD team each) on the exact fp32 VALU
+        # lstm_team.h plan_exact(): the sequences run as chains of ≤ 8 rows (one XCD team each) on the exact fp32 VALU
         # recurrence at every B; beyond 64 the chains queue, and the queue holds 32 (raises here, ahead of any launch)
         team_plan(B, True, True)
     # sequence packing (learner/ingest.py): per-(step, row) episode-start flags, time-major (S, B) u8 — the team

@@ -220,7 +220,7 @@ class Policy(nn.Module):
 
     def recurrent(self, x: torch.Tensor, hidden=None, reset: Optional[torch.Tensor] = None):
         """``reset`` (B, S) bool/u8, sequence packing: an episode starts at step t of row b — its h, c are zero
-        before that step (the oracle of the fused recurrence's reset flags, ops/csrc/lstm_team.hip)."""
+        before that step (the oracle of the fused recurrence's reset flags, ops/csrc/lstm_team_fwd.hip, lstm_team_bwd.hip)."""
         if self.config.rnn == 'linear':
             return self.fake_rnn(x), hidden
         if hidden is None:

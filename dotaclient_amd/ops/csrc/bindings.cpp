@@ -193,7 +193,7 @@ inline unsigned long long* trace_ptr(const c10::optional<torch::Tensor>& t, int6
 
 
 // ------------------------------------------------------------------------------------------------------------
-// XCD-team LSTM recurrence (lstm_team.hip). Gates in unit-major (·,·,H,4) layout; see the kernel header.
+// XCD-team LSTM recurrence (lstm_team_fwd.hip, lstm_team_bwd.hip). Gates in unit-major (·,·,H,4) layout; see lstm_team.h.
 // whh bf16: bf16 MFMA, h exchanged in bf16 (hs bf16, optional f32 copy); whh fp32: the fp32-accurate variant
 // (bf16x3 split MFMA, h exchanged in fp32; returns hs f32 in both hs slots).
 // time_major=false: xp4 (B,S,H,4) and outputs (B,S,…); time_major=true: xp4 (S,B,H,4) and outputs (S,B,…) — a
@@ -225,7 +225,7 @@ inline void check_ctl(const torch::Tensor& ctl) {
               "team control block too small (use ops.lstm.team_ctl())");
 }
 
-// exact / rows (lstm_team.hip plan_exact): refused here, before any allocation or launch, when they name no plan
+// exact / rows (lstm_team.h plan_exact): refused here, before any allocation or launch, when they name no plan
 inline void check_team_plan(int B, bool f32w, bool exact, int64_t rows, const char* who) {
   TORCH_CHECK(rows >= 0 && rows <= 8 && dca_lstm_team_chains(B, f32w ? 1 : 0, exact ? 1 : 0, (int)rows) >= 0, who,
               ": no launch plan for B = ", B, ", exact = ", exact, ", rows = ", rows,

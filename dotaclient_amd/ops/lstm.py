@@ -1,4 +1,5 @@
-"""Launch helpers of the XCD-team persistent LSTM recurrence kernels (ops/csrc/lstm_team.hip).
+"""Launch helpers of the XCD-team persistent LSTM recurrence kernels (ops/csrc/lstm_team.h, lstm_team_fwd.hip,
+lstm_team_bwd.hip).
 
 * ``team_fwd`` — the recurrence in ONE persistent launch (``_C.lstm_team_fwd``): 32 workgroups of ONE XCD per
   sequence chain, exchanging the step state through that XCD's L2, gates in unit-major (…, H, 4) layout; it saves the
@@ -58,7 +59,7 @@ _CTL = {}
 
 def team_ctl(device=None, stream=None) -> torch.Tensor:
     """The persistent, self-cleaning control block for team-LSTM launches on (device, stream): zero-initialised
-    once; each launch leaves it clean for the next one and advances its epoch (lstm_team.hip ``TeamCtl``). Team
+    once; each launch leaves it clean for the next one and advances its epoch (lstm_team.h ``TeamCtl``). Team
     kernels on different streams must not share a block, kernels on one stream are serialised anyway."""
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     if dev.index is None:
@@ -138,14 +139,14 @@ def merge_team_stats(parsed) -> dict:
     return out
 
 
-TEAMS = 8                              # XCD teams of a launch (lstm_team.hip kMaxTeams)
+TEAMS = 8                              # XCD teams of a launch (lstm_team.h kMaxTeams)
 EXACT_ROWS = (1, 2, 4, 8)              # rows per chain of the exact VALU forms the build dispatches
-EXACT_MAX_CHAINS = 32                  # queue bound of the exact plan (lstm_team.hip kMaxQueue, at make_tagbase)
+EXACT_MAX_CHAINS = 32                  # queue bound of the exact plan (lstm_team.h kMaxQueue, at make_tagbase)
 EXACT_MAX_BATCH = EXACT_MAX_CHAINS * EXACT_ROWS[-1]
 
 
 def team_plan(B: int, f32: bool, exact: bool, rows: int = 0):
-    """``(nch, Bc)`` of a team-recurrence launch of ``B`` sequences: the pure-Python mirror of lstm_team.hip
+    """``(nch, Bc)`` of a team-recurrence launch of ``B`` sequences: the pure-Python mirror of lstm_team.h
     ``plan()`` / ``plan_exact()``. Chain ``c`` holds the sequences ``[c·Bc, min((c + 1)·Bc, B))`` (empty where that
     range is); a chain of ``Bc`` rows runs the next kernel form up (1, 2, 4, 8 rows).
 

@@ -1,10 +1,10 @@
 // Microbenchmark: does the L2 placement of a team's exchange buffer bound the per-step all-gather latency?
 // T workgroups of ONE XCD (blockIdx ≡ 0 mod 8 under the round-robin dispatch; checked with HW_REG_XCC_ID) each
 // publish G tagged 8-B granules per step (plain stores) and gather all T·G granules (sc1 16-B polls, one chunk per
-// thread per round, re-polling only missing chunks — the lstm_team.hip protocol), then __syncthreads. No compute.
+// thread per round, re-polling only missing chunks — the lstm_team.h protocol), then __syncthreads. No compute.
 // The gathered region is laid out as 128-B lines (8 chunks) placed `stride` bytes apart: stride 128 = contiguous
 // (today's layout), larger strides put consecutive lines in other L2 channels / pages if the channel hash uses those
-// address bits. Also: T = 16 vs 32 members at the same gathered bytes (team-size question, lstm_team.hip kT).
+// address bits. Also: T = 16 vs 32 members at the same gathered bytes (team-size question, lstm_team.h kT).
 // Build: hipcc --offload-arch=gfx950 -O3 scripts/ubench/xcd_gather_layout.hip -o scripts/ubench/xcd_gather_layout
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -1,4 +1,4 @@
-"""fp32-exact beyond 32 sequences per step and GPU: the exact plan of the team recurrence (ops/csrc/lstm_team.hip
+"""fp32-exact beyond 32 sequences per step and GPU: the exact plan of the team recurrence (ops/csrc/lstm_team.h
 ``plan_exact``: exact VALU chains of 1 / 2 / 4 / 8 rows at every batch size, queued behind the 8 running ones beyond
 8 × 8 sequences, at most 32 chains) from the launch plan up to ``DotaOptimizer``.
 
@@ -21,7 +21,7 @@ BIG_ROWS = [r for r in (4, 8) if r in EXACT_ROWS]        # the row forms that qu
 
 # ------------------------------------------------------------------------------------------------ CPU: the plan
 def _old_plan(B, f32):
-    """plan() of lstm_team.hip as it stood before the exact plan."""
+    """plan() of lstm_team.h as it stood before the exact plan."""
     nch = min(B, 8) if B <= 8 * 32 else (B + 31) // 32
     if f32 and (B + nch - 1) // nch > 16:
         nch = (B + 15) // 16

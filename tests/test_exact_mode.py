@@ -102,7 +102,7 @@ def test_exact_fused_step_deploy_shape_matches_fp64(gpu_ops, algo, B):
     evaluation itself under VPG and at B = 16 / 32 (the conditioning of that 11 200 × 8-row sum, not the kernels):
     there a tensor may reach 1.5× the torch-fp32 error instead (measured: fused 1.01e-5 vs torch 1.22e-5 VPG B=8,
     1.03e-5 vs 1.05e-5 PPO B=16, 1.09e-5 vs 1.26e-5 PPO B=32). B = 16 / 32: the exact recurrence with 2 / 4 rows per
-    XCD chain (lstm_team.hip V1 rows)."""
+    XCD chain (lstm_team.h: the Valu forms' rows)."""
     from tests.test_fp32_kernels import _rel, _step_grads
     (lf, _, gf), (lo, _, go), (l64, g64) = _step_grads('fp32-exact', 'lstm512', algo, B, 1400, fp64=True)
     rows = sorted(((_rel(gf[n], g64[n]), _rel(go[n], g64[n]), n) for n in g64

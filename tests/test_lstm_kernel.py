@@ -1,4 +1,4 @@
-"""XCD-team persistent LSTM recurrence kernels (ops/csrc/lstm_team.hip) vs an fp32 torch ``nn.LSTM`` reference."""
+"""XCD-team persistent LSTM recurrence kernels (ops/csrc/lstm_team_fwd.hip, lstm_team_bwd.hip) vs an fp32 torch ``nn.LSTM`` reference."""
 import pytest
 import torch
 
@@ -12,7 +12,7 @@ def gpu_C():
     return require()
 
 # --- test glue: an nn.LSTM-shaped autograd wrapper around the team kernels (input projection and the weight
-# gradients as torch GEMMs, the recurrence forward / backward on lstm_team.hip)
+# gradients as torch GEMMs, the recurrence forward / backward on lstm_team_fwd.hip / lstm_team_bwd.hip)
 def _mm_f32(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """bf16 × bf16 → fp32 GEMM (torch, test glue only) — fp32 accumulation and output."""
     return torch.mm(a.to(torch.bfloat16), b.to(torch.bfloat16), out_dtype=torch.float32)

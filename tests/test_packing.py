@@ -5,7 +5,7 @@
 * the packer's placement: first fit into free tails, long / stored-state rollouts aligned, reset rows, h0 sources;
 * the CPU oracle (torch LSTM with resets, models/policy.py) — a packed sequence [A | B] gives the same PPO loss and
   parameter gradients as the padded sequences [A], [B];
-* GPU: the fused learner step with the team recurrence's reset flags (ops/csrc/lstm_team.hip) against the same
+* GPU: the fused learner step with the team recurrence's reset flags (ops/csrc/lstm_team_fwd.hip, lstm_team_bwd.hip) against the same
   padded evaluation, fp32 (bf16x3) and IEEE fp32."""
 import copy
 

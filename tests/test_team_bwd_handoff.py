@@ -1,6 +1,6 @@
 """The exact-fp32 (V1 / V2) team backward with the ∂h hand-off: an owner publishes one {∂h_t, tag} granule per (row,
 unit) and every wave of every workgroup turns the granules of its own K part into gate gradients itself, from saved
-activations it prefetched, with the cell-gradient carry as per-lane state (ops/csrc/lstm_team.hip). Checked here,
+activations it prefetched, with the cell-gradient carry as per-lane state (ops/csrc/lstm_team_bwd.hip). Checked here,
 against the float64 recurrence and with the tolerances of test_team_wave_gather.py: final-state gradients (the
 consumer-side carry starts from dcn in every workgroup) at the shapes where the publish-only first iteration, the final
 iteration that now also produces ∂gates[0] and ∂c0, lanes without a unit and 2 / 4 rows of per-lane carry can go wrong;

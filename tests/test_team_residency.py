@@ -1,6 +1,6 @@
 """The XCD-team recurrence beside resident kernels (VERDICT r5 weak #8 / next #5b).
 
-A team is the 32 workgroups of one XCD (one per CU), formed from HW_REG_XCC_ID tickets (ops/csrc/lstm_team.hip
+A team is the 32 workgroups of one XCD (one per CU), formed from HW_REG_XCC_ID tickets (ops/csrc/lstm_team.h
 ``join_team``); chains are pulled from a queue. When part of one XCD is held by another kernel — an actor replay, a
 collective, another process — that XCD's team cannot gather its 32 members: its leader gives up after a bounded wait
 (state 2, no error), the other XCDs' teams drain the chain queue, and the results are the SAME bits (a chain's

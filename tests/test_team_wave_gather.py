@@ -1,10 +1,12 @@
 """The exact-fp32 (V1 / V2) team recurrences with the backward's wave-private gather: every wave of a workgroup
 polls only the chunks of its own K part of ∂G_{t+1} and no workgroup barrier stands between that gather and the
-partial product (ops/csrc/lstm_team.hip). Checked here: forward and backward against a float64 recurrence at the
+partial product (ops/csrc/lstm_team_bwd.hip). Checked here: forward and backward against a float64 recurrence at the
 shapes where the first step (no gather), the first gather and the final ∂h0 iteration, waves without units, uneven
 chains and the 2- and 4-row forms can go wrong; episode-start flags; row b of a B-row launch bitwise equal to that
 row launched alone (a wave that read bytes it did not fetch itself shows up here); back-to-back and hipGraph-replayed
-launches bitwise equal (control block, tags and LDS images survive relaunches); the error word stays 0."""
+launches bitwise equal (control block, tags and LDS images survive relaunches); the error word stays 0. The
+``precise`` (libm activation) forms of the one-row chains at each H go through the same float64 check, and ``precise``
+with more rows per chain, for which no kernel exists, is refused before anything runs."""
 import pytest
 import torch
 
@@ -14,7 +16,11 @@ pytestmark = pytest.mark.gpu
 # that own no units, other K parts; B = 9 — uneven two-row chains; B = 16 / 32 — two / four rows per chain
 SHAPES = [(1, 1, 512), (1, 2, 512), (8, 33, 512), (3, 40, 128), (5, 17, 256), (9, 20, 128), (16, 12, 512),
           (32, 9, 512)]
-CASES = [(s, True) for s in SHAPES] + [((8, 33, 512), False), ((3, 40, 128), False)]
+# precise: one-row chains at each H (H = 512: the backward's eight-wave form)
+PRECISE_SHAPES = [(3, 5, 128), (2, 5, 256), (8, 5, 512)]
+CASES = ([(s, True, False) for s in SHAPES] + [((8, 33, 512), False, False), ((3, 40, 128), False, False)] +
+         [(s, True, True) for s in PRECISE_SHAPES])
+CASE_IDS = [f'shape{i}-{tm}' + ('-precise' if p else '') for i, (_, tm, p) in enumerate(CASES)]
 
 
 def _rel(a, b):
@@ -72,7 +78,7 @@ def _starts(B, S):
     return r.cuda()
 
 
-def _launch(C, d, time_major=True, reset=None, rows=None):
+def _launch(C, d, time_major=True, reset=None, rows=None, precise=False):
     """One forward + backward pair; returns the outputs in time-major order (views for batch-major launches)."""
     from dotaclient_amd.ops.lstm import team_bwd, team_fwd
     sel = (lambda x, dim: x) if rows is None else (lambda x, dim: x.narrow(dim, rows, 1).contiguous())
@@ -82,9 +88,9 @@ def _launch(C, d, time_major=True, reset=None, rows=None):
     rs = None if reset is None else lay(sel(reset, 1))
     err = torch.zeros(1, dtype=torch.int32, device='cuda')
     hs, _, cs, gates, hn, cn = team_fwd(C, xp, d['whh'], h0, c0, err, False, time_major=time_major, bias4=d['bias'],
-                                        reset=rs)
+                                        reset=rs, precise=precise)
     dg, dh0, dc0, db = team_bwd(C, dh, gates, cs, c0, None, None, d['whh'], err, time_major=time_major,
-                                want_dbias=True, reset=rs)
+                                want_dbias=True, reset=rs, precise=precise)
     tm = (lambda x: x) if time_major else (lambda x: x.transpose(0, 1))
     return {'hs': tm(hs), 'cs': tm(cs), 'gates': tm(gates), 'hn': hn, 'cn': cn, 'dg': tm(dg), 'dh0': dh0, 'dc0': dc0,
             'db': db, 'err': err}
@@ -120,10 +126,28 @@ def _check(out, ref):
         assert _rel(out[k], ref[k]) < 1e-4, (k, _rel(out[k], ref[k]))
 
 
-@pytest.mark.parametrize('shape,time_major', CASES)
-def test_wave_gather_matches_float64(gpu_ops, shape, time_major):
+@pytest.mark.parametrize('shape,time_major,precise', CASES, ids=CASE_IDS)
+def test_wave_gather_matches_float64(gpu_ops, shape, time_major, precise):
     d, _, ref = _reference(*shape, False)
-    _check(_launch(gpu_ops, d, time_major=time_major), ref)
+    _check(_launch(gpu_ops, d, time_major=time_major, precise=precise), ref)
+
+
+def test_precise_needs_one_row_chains(gpu_ops):
+    """fp32 weights, B = 16: two rows per chain. There is no libm-activation kernel for them, so forward and backward
+    raise, and nothing ran that could have set the error word."""
+    from dotaclient_amd.ops.lstm import team_bwd, team_fwd
+    d = _inputs(16, 3, 512)
+    err = torch.zeros(1, dtype=torch.int32, device='cuda')
+    with pytest.raises(RuntimeError):
+        team_fwd(gpu_ops, d['xp'], d['whh'], d['h0'], d['c0'], err, False, time_major=True, bias4=d['bias'],
+                 precise=True)
+    hs, _, cs, gates, _, _ = team_fwd(gpu_ops, d['xp'], d['whh'], d['h0'], d['c0'], err, False, time_major=True,
+                                      bias4=d['bias'])
+    with pytest.raises(RuntimeError):
+        team_bwd(gpu_ops, d['dh'], gates, cs, d['c0'], None, None, d['whh'], err, time_major=True, want_dbias=True,
+                 precise=True)
+    torch.cuda.synchronize()
+    assert int(err.item()) == 0
 
 
 @pytest.mark.parametrize('shape', [(8, 33, 512), (9, 20, 128)])
