@@ -287,12 +287,14 @@ __device__ __forceinline__ void lstm_team_bwd_body(
         } else if constexpr (kActsAhead) {
           load_acts(t);
         }
-      } else if (t >= 0) {
+      } else {
 #pragma unroll
         for (int i = 0; i < NPAIR; ++i) {
           const int pi = tid + NT * i;
           rcur[i] = rnext[i] = false;
-          if (pi < B * U) {
+          gv[i] = dca::f32x4{0.f, 0.f, 0.f, 0.f};       // (defined on every path: every thread lands them below)
+          cv[i] = cpv[i] = dv[i] = 0.f;
+          if (t >= 0 && pi < B * U) {
             const int b = pi / U, u = pi % U;
             const size_t bt = (size_t)(b0 + b) * sb + (size_t)t * st;
             gv[i] = *reinterpret_cast<const dca::f32x4*>(gates4 + (bt * H + j0 + u) * 4);
@@ -443,6 +445,14 @@ __device__ __forceinline__ void lstm_team_bwd_body(
             }
           }
         }
+      }
+      // The forms on the ∂gates exchange: land the step's activation prefetch here, behind the gather, as the forward
+      // lands its own (lstm_team_fwd.hip). A polling thread has just waited vmcnt(0), so nothing is outstanding; left
+      // to the compiler, "may be in flight" goes round the back edge and the next step's loads into these registers
+      // wait out all but the last three of this step's stores at the top of the step. Outside any branch.
+      if constexpr (!HO) {
+#pragma unroll
+        for (int i = 0; i < NPAIR; ++i) asm volatile("" ::"v"(gv[i]), "v"(cv[i]), "v"(cpv[i]), "v"(dv[i]));
       }
       TSTAMPB(1);
       if constexpr (V1) {

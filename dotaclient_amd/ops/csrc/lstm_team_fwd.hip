@@ -14,6 +14,10 @@
 // VGPRs) and runs pk_dot4 per row, row_sum16 sums the 16 slices into every lane of the unit's group → activations and
 // cell update for every row in every lane of the group (8 rows: one row at a time) → the slice-r lane publishes row
 // r's granule → c and h leave in one store instruction (slice 2r: row r's c and gates, slice 2r + 1: its h).
+// Waits on vector memory in a step, every form: the poll's, those of the t = 0 copy and the time-out path, and one
+// landing of the step's prefetch behind the gather (free behind a poll). None between a step's stores and the next
+// step's first poll: until profiles/recurrence_fwd_waits.md the compiler placed two vmcnt(0) per step for a chain-start
+// load left pending (scripts/asm_step_waits.py lists them), and every forward measurement older than that carried them.
 #include "lstm_team.h"
 
 namespace {
@@ -148,6 +152,15 @@ __device__ __forceinline__ void lstm_team_fwd_body(
       creg[i] = (mfma_wave && b < B) ? c0[(size_t)(b0 + b) * H + eunit] : 0.f;
       hreg[i] = 0.f;
     }
+    // Land the chain-start loads here, once per chain (the technique of lstm_team_bwd.hip, ccv): left pending into the
+    // step loop, the compiler's wait-count merge at the loop header takes creg for a load in flight in EVERY
+    // iteration — a vmcnt(0) ahead of the product (read of the loop-carried copy) and one at the back edge (write
+    // into it), the second behind the publish and the output stores, so that every wave waited out their
+    // acknowledgement before it issued the next step's prefetch and first poll. The bias vector is loaded once per
+    // launch and read in every step in the same way. Hazards: profiles/recurrence_fwd_waits.md.
+#pragma unroll
+    for (int i = 0; i < NR; ++i) asm volatile("" ::"v"(creg[i]));
+    asm volatile("" ::"v"(bv));
     bool dead = false;
     for (int t = 0; t < S; ++t) {
       const int par = t & 1;
@@ -169,8 +182,15 @@ __device__ __forceinline__ void lstm_team_fwd_body(
           xv[i] = (b < B) ? *reinterpret_cast<const dca::f32x4*>(xp4 + (((size_t)(b0 + b) * sb + tx * st) * H + eunit) * 4)
                           : dca::f32x4{0.f, 0.f, 0.f, 0.f};
           rzb[i] = 0;
-          if (rst != nullptr)                           // (uniform; rows >= B read row 0's flag and are never stored)
-            rzb[i] = rst[(size_t)(b0 + (b < B ? b : 0)) * sb + (size_t)t * st];
+          if (rst != nullptr)                           // (uniform; rows >= B read sequence 0's flag and are never
+            rzb[i] = rst[(size_t)(b < B ? b0 + b : 0) * sb + (size_t)t * st];   // stored. Not b0's: the plan's last
+                                                        // chain may be empty, b0 ≥ Btot, and its flag past the end)
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {                  // (defined in every wave: all of them land it below)
+          xv[i] = dca::f32x4{0.f, 0.f, 0.f, 0.f};
+          rzb[i] = 0;
         }
       }
       // ---- gather h_{t-1} into hl[par]
@@ -240,6 +260,15 @@ __device__ __forceinline__ void lstm_team_fwd_body(
           }
         }
       }
+      // Land the step's prefetch (xv, the reset byte) here, behind the gather. At t > 0 a polling wave has just waited
+      // vmcnt(0) for its last poll round and returns are in order, so this wait finds nothing outstanding; at t = 0
+      // and in a wave with no chunk to poll it is the wait the step needs anyway. Without it the compiler carries
+      // "xv / rzb may be in flight" round the back edge (the paths with no poll have no wait) and protects next step's
+      // writes into these registers at the top of the step: vmcnt(1) behind the xv prefetch when no reset tensor is
+      // passed, which drains the publish and the output stores ahead of the first poll exactly as the back-edge wait
+      // did. In every wave and outside any branch: a path round it would keep the registers "in flight".
+#pragma unroll
+      for (int i = 0; i < NR; ++i) asm volatile("" ::"v"(xv[i]), "v"(rzb[i]));
       TSTAMP(1);
       if (dead) sh_int = -2;
       lds_barrier();
@@ -415,6 +444,20 @@ __device__ __forceinline__ void lstm_team_fwd_body(
           TSTAMP(5);
         }
       }
+      // Back edge: no wait on vector memory here (the compiler used to place vmcnt(0), see the landing of creg above).
+      // The publish and the output stores of step t are still in flight when step t + 1 issues its prefetch and its
+      // first poll. Nothing relied on that drain:
+      // * hand-off: a granule carries data and tag in ONE 8-byte store, so a consumer that sees tag t + 1 sees h_t;
+      //   no later store of this wave completes or orders it.
+      // * slot reuse: the parity slot of step t is written again at t + 2. A wave gets there only behind its gather of
+      //   step t + 2, i.e. after EVERY workgroup published t + 1, which each did behind its own gather of t + 1 — its
+      //   last read of slot t. Program order per wave plus the tags, not vmcnt.
+      // * outputs (h / c / gates, hn / cn): never read back by this kernel; the launch's end makes them visible.
+      //   xv and the reset byte are read-only inputs. Registers: a store reads its data when it issues.
+      // * vmcnt returns are in order, so step t + 1's poll wait still covers these stores; what is gone is waiting for
+      //   them BEFORE the poll is issued.
+      // * the dead → sh_int = -2 → break hand-shake runs on LDS and the barrier; the chain-end stores (hn, cn, the
+      //   `done` counter behind __syncthreads) and next_chain's control-block loads keep their own waits.
     }
 #undef TSTAMP
     if (sh_int == -2) return;
