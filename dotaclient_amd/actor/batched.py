@@ -11,6 +11,7 @@ h/c) lives on the GPU in fixed slots and one step of *all* slots is a captured g
                                              relu(x896·W_preᵀ + b), gates = [x | h]·[W_ih | W_hh]ᵀ + b + LSTM cell
                                              (or the fake_rnn Linear), z = h·W_headsᵀ + b for all 5 heads
     sample_actions                           fused masked log-softmax + Gumbel-max + hierarchical selection
+                                             (``temperature=True``: at a per-slot temperature τ, 0 = greedy arg-max)
     D2H(idx, logp, value[, act, msk])
 
 No vendor GEMM in any actor step: bf16 operands (:class:`GpuActorPolicy`, the default), IEEE fp32 on the f32 MFMA
@@ -114,7 +115,40 @@ def build_set_plan(h_set, n_sets: int, rows_out: np.ndarray, tile_set_out: np.nd
     return tile
 
 
-class GpuActorPolicy:
+TEMP_MIN, TEMP_MAX = 1e-3, 1e3
+
+
+def check_temperature(value) -> np.ndarray:
+    """Sampling temperatures as fp32: each finite and either 0 (greedy: the arg-max action, behaviour log-prob 0) or
+    within [TEMP_MIN, TEMP_MAX] (the masked softmax of logits / τ). Raises ``ValueError`` otherwise — a τ below
+    ``TEMP_MIN`` should ask for greedy."""
+    t = np.asarray(value, dtype=np.float64)
+    ok = np.isfinite(t) & ((t == 0.0) | ((t >= TEMP_MIN) & (t <= TEMP_MAX)))
+    if not bool(np.all(ok)):
+        raise ValueError(f'temperature must be finite and 0 (greedy) or within [{TEMP_MIN:g}, {TEMP_MAX:g}], got '
+                         f'{np.asarray(value).tolist()!r}')
+    return t.astype(np.float32)
+
+
+class _Temperature:
+    """``set_temperature`` of the slot policies (``h_temp``: the (n,) fp32 host vector the next step reads)."""
+
+    def set_temperature(self, value, rows=None):
+        """Per-slot sampling temperature from the next step on — a scalar or an array (all slots, or ``rows``): τ > 0
+        samples from the masked softmax of logits / τ and reports its log-prob; 0 plays the arg-max action (lowest
+        index on ties) with log-prob 0. Validated on the host (:func:`check_temperature`); a captured step is not
+        recaptured."""
+        if getattr(self, 'h_temp', None) is None:
+            raise RuntimeError('set_temperature: build the policy with temperature=True')
+        t = check_temperature(value)
+        dst = self.h_temp.numpy()
+        if rows is None:
+            dst[:] = t
+        else:
+            dst[np.asarray(rows)] = t
+
+
+class GpuActorPolicy(_Temperature):
     """Fixed-slot batched policy step on one GPU: LSTM / linear-RNN policies, 1v1 or 5v5 (entity attention), bf16
     operands on hand-written MFMA kernels (``CORE_MODE`` 1; :class:`F32ActorPolicy` is the IEEE-fp32 twin).
 
@@ -123,15 +157,20 @@ class GpuActorPolicy:
     one core and one sampler launch: the kernels' 16-row tiles are gathered from slots that share a set
     (:func:`build_set_plan`, rebuilt when ``h_set`` changed); the 5v5 attention block runs one workgroup per slot and
     takes the slot's set directly (the plan's ``slot_set`` region). A slot changes its set together with a reset of
-    its state."""
+    its state.
+
+    ``temperature=True``: the sampler takes a per-slot temperature ``h_temp`` (:meth:`set_temperature`; all 1 at
+    first, which is bit for bit the step without it), staged with the step's inputs — changing it between steps
+    needs no recapture. Off (the default): the pack, the captured graph and the kernel are those without the option."""
 
     CORE_MODE = 1        # ops/csrc/actor_core.hip: 0 = IEEE fp32 (f32 MFMA), 1 = bf16 operands
 
     def __init__(self, policy: Policy, n_slots: int, device='cuda', seed: int = 0, use_graph: bool = True,
                  record: bool = True, inputs_from: Optional['GpuActorPolicy'] = None, raw: bool = False,
-                 n_sets: int = 1):
+                 n_sets: int = 1, temperature: bool = False):
         from .. import ops
         self.C = ops.require()
+        self.temperature = bool(temperature)
         self.n_sets = int(n_sets)
         if self.n_sets < 1:
             raise ValueError('n_sets must be >= 1')
@@ -179,6 +218,13 @@ class GpuActorPolicy:
         self.h_keep.fill_(1.0)
         self.h_active.fill_(1.0)
         self._in_last = 'active'                       # last region of the step's one H2D copy
+        self.h_temp = self.d_temp = None
+        if self.temperature:
+            # per-slot sampling temperature: directly after 'active', so it crosses in the same copy
+            self.h_temp, self.d_temp = self.in_pack.host['temp'], self.in_pack.dev['temp']
+            self.h_temp.fill_(1.0)
+            self._in_last = 'temp'
+        self._own_last = self._in_last                 # last per-policy region when the observations are shared
         self._plan_kw = {}
         if self.n_sets > 1:
             # per-slot weight set (staged by the caller) and the launch plan built from it: the plan's two regions
@@ -203,7 +249,7 @@ class GpuActorPolicy:
         n, U, dev = self.n, self.U, self.device
         self.in_pack = _Pack([('env', (n, 3), torch.float32), ('hero', (n, 4), torch.float32),
                               ('raw', (n, U, self.RAW_WORDS), torch.int32), ('keep', (n, 1), torch.float32),
-                              ('active', (n,), torch.float32)] + self._plan_fields(), dev)
+                              ('active', (n,), torch.float32)] + self._temp_fields() + self._plan_fields(), dev)
         if inputs_from is not None:
             if (inputs_from.n, inputs_from.U) != (n, U) or not inputs_from.raw:
                 raise ValueError('inputs_from: slot count / layout / staging mismatch')
@@ -224,7 +270,7 @@ class GpuActorPolicy:
         # and its outputs come back in one (each separate copy was a DMA dispatch of its own inside the graph)
         self.in_pack = _Pack([('env', (n, 3), torch.float32), ('units', (n, U, 10), ud), ('handles', (n, U), hd),
                               ('keep', (n, 1), torch.float32), ('active', (n,), torch.float32)]
-                             + self._plan_fields(), dev)
+                             + self._temp_fields() + self._plan_fields(), dev)
         if inputs_from is not None:
             # a second policy over the same observations (league opponents): share the staged inputs; keep/active
             # stay per policy (its own pack's env / units / handles regions are unused)
@@ -238,6 +284,9 @@ class GpuActorPolicy:
         # the kernels read the staged dtypes as they are (fp8 step: fp16 features, int32 handles)
         self.d_units = self.in_pack.dev['units']
         self.d_handles = self.in_pack.dev['handles']
+
+    def _temp_fields(self):
+        return [('temp', (self.n,), torch.float32)] if self.temperature else []
 
     def _plan_fields(self):
         if self.n_sets == 1:
@@ -423,7 +472,7 @@ class GpuActorPolicy:
                      self.d_keep.view(-1), self.z, self.CORE_MODE, cfg.rnn != 'lstm', active=self.d_active,
                      bump=self.ctr, **self._plan_kw)
         C.sample_actions(self.z, emb, self.d_handles, self.seed, self.ctr, self.idx, self.act, self.msk, self.logp,
-                         self.value)
+                         self.value, temp=self.d_temp)
 
     def _h2d(self):
         if self._shared_inputs:
@@ -436,7 +485,7 @@ class GpuActorPolicy:
             else:
                 ip['units'].copy_(self.h_units, non_blocking=True)
                 ip['handles'].copy_(self.h_handles, non_blocking=True)
-            self.in_pack.copy_range('keep', 'active')
+            self.in_pack.copy_range('keep', self._own_last)
         else:
             self.in_pack.copy_range('env', self._in_last)     # one H2D copy of the whole staged step
 
@@ -666,18 +715,19 @@ class Fp8ActorPolicy(GpuActorPolicy):
         C.actor_fp8(x896, w['wpre8'], w['spre'], w['bpre32'], w['wg8'], w['sg'], w['bg'], w['wh8'], w['sh8'],
                     w['bh'], self.h, self.c, self.d_keep.view(-1), self.z, self.d_active, self.ctr, **self._plan_kw)
         C.sample_actions(self.z, emb, self.d_handles, self.seed, self.ctr, self.idx, self.act, self.msk, self.logp,
-                         self.value)
+                         self.value, temp=self.d_temp)
 
 
-class TorchSlotPolicy:
+class TorchSlotPolicy(_Temperature):
     """:class:`GpuActorPolicy`'s host interface (staged ``h_*`` inputs, per-slot LSTM state, ``keep``/``active``,
     :meth:`step_async`/:meth:`wait`, hidden snapshots) over the eager torch policy on any device — the CPU actor
     (BASELINE config 1: no GPU) and policies the fused graph does not cover (5v5 entity attention).
     ``n_sets > 1``: one eager policy per weight set (``load_weights(state, set=k)``), each stepping the active slots
-    whose ``h_set`` names it — the mixed step's host interface without a GPU."""
+    whose ``h_set`` names it — the mixed step's host interface without a GPU. ``temperature=True``: the per-slot
+    sampling temperature ``h_temp`` (:meth:`set_temperature`), as :class:`GpuActorPolicy`."""
 
     def __init__(self, policy: Policy, n_slots: int, device='cpu', seed: int = 0, record: bool = True,
-                 inputs_from: Optional['TorchSlotPolicy'] = None, n_sets: int = 1, **_):
+                 inputs_from: Optional['TorchSlotPolicy'] = None, n_sets: int = 1, temperature: bool = False, **_):
         from .runner import PolicyRunner
         self.cfg = policy.config
         self.n = n_slots
@@ -708,6 +758,8 @@ class TorchSlotPolicy:
             self.h_handles = torch.full((n, U), -1, dtype=torch.long)
         self.h_keep = torch.ones(n, 1)
         self.h_active = torch.ones(n)
+        self.temperature = bool(temperature)
+        self.h_temp = torch.ones(n) if self.temperature else None
         H = self.cfg.hidden
         self.recurrent = self.cfg.rnn == 'lstm'
         self.h = np.zeros((n, H), np.float32)
@@ -741,7 +793,9 @@ class TorchSlotPolicy:
             if not len(act):
                 continue
             hid = (self.h[act], self.c[act]) if self.recurrent else None
-            o, nh = runner.step(self.h_env.numpy()[act], self.h_units.numpy()[act], self.h_handles.numpy()[act], hid)
+            temp = self.h_temp.numpy()[act] if self.temperature else None
+            o, nh = runner.step(self.h_env.numpy()[act], self.h_units.numpy()[act], self.h_handles.numpy()[act], hid,
+                                temperature=temp)
             out['idx'][act] = np.stack([o.enum, o.x, o.y, o.target], 1)
             out['logp'][act], out['value'][act] = o.logp, o.value
             out['actions'][act], out['masks'][act] = o.actions, o.masks

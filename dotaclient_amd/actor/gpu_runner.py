@@ -14,6 +14,8 @@ of one policy object from a graph-captured :class:`~dotaclient_amd.actor.batched
 * weight updates are picked up by version (``policy.weight_version``, set by the WeightStore) and loaded in place,
   so the captured graph stays valid; capacity doubles on demand (re-capture, state carried over).
 
+``temperature`` (a scalar; 1: the policy's softmax, 0: greedy arg-max) is the sampling temperature of every slot.
+
 ``step(env, units, handles, hidden)`` keeps the stateless :class:`~dotaclient_amd.actor.runner.PolicyRunner` API
 (host hidden in, new hidden out) for callers that manage the state themselves.
 """
@@ -41,13 +43,15 @@ class GpuRunner:
     stateful = True
 
     def __init__(self, policy: Policy, device='cuda', seed: int = 0, capacity: int = 64,
-                 use_graph: bool = True):
+                 use_graph: bool = True, temperature: float = 1.0):
+        from .batched import check_temperature
         if not gpu_runner_supported(policy):
             raise ValueError('GpuRunner: policy not covered by the batched GPU actor (see gpu_runner_supported)')
         self.policy = policy
         self.device = torch.device(device)
         self.seed = int(seed)
         self.use_graph = use_graph
+        self.temperature = float(check_temperature(temperature))
         self.recurrent = policy.config.rnn == 'lstm'
         self.H = policy.config.hidden
         self.slots: Dict[Hashable, int] = {}
@@ -67,7 +71,9 @@ class GpuRunner:
     def _grow(self, cap: int):
         old = self.gp
         gp = GpuActorPolicy(self.policy, cap, device=self.device, seed=self.seed, use_graph=self.use_graph,
-                            record=True)
+                            record=True, temperature=self.temperature != 1.0)
+        if gp.temperature:
+            gp.set_temperature(self.temperature)
         if self.use_graph:
             gp.capture()                 # capture zeroes the slot state: do it before carrying the old state over
         if old is not None:

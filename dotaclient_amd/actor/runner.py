@@ -43,20 +43,40 @@ class StepOutput:
         return d
 
 
-def sample_heads(logits: dict, valid: torch.Tensor, U: int, generator=None, stable: bool = True):
-    """Sample (enum, x, y, target) for every row; returns tensors + flat one-hot actions/selected masks + logp."""
+def sample_heads(logits: dict, valid: torch.Tensor, U: int, generator=None, stable: bool = True, temperature=None):
+    """Sample (enum, x, y, target) for every row; returns tensors + flat one-hot actions/selected masks + logp.
+
+    ``temperature``: optional per-row τ (a scalar or (n,)), the sampling kernel's semantics (ops/csrc/actor.hip). τ > 0:
+    every head is drawn from the masked softmax of (logits − masked max) / τ and ``logp`` is the log-prob under that
+    tempered distribution (the behaviour policy). Otherwise the row is greedy: every head takes the arg-max of its
+    masked logits (lowest index on ties) and ``logp`` is 0, the τ → 0 limit. The masks do not depend on τ."""
     n = valid.shape[0]
+    greedy = inv_tau = None
+    if temperature is not None:
+        tau = torch.as_tensor(temperature, dtype=torch.float32, device=valid.device).reshape(-1).expand(n)
+        greedy = ~(tau > 0)
+        inv_tau = (1.0 / torch.where(greedy, torch.ones_like(tau), tau))[:, None]
     offs = {'enum': (0, 3), 'x': (3, N_MOVE_ENUMS), 'y': (3 + N_MOVE_ENUMS, N_MOVE_ENUMS),
             'target_unit': (3 + 2 * N_MOVE_ENUMS, U)}
     samples, logps = {}, {}
     for k, (o, w) in offs.items():
         m = valid[:, o:o + w]
-        lp = masked_log_softmax(logits[k].reshape(n, w).float(), m, dim=-1, stable=stable)
+        lg = logits[k].reshape(n, w).float()
+        if inv_tau is not None:
+            # scaled after the masked maximum is subtracted (a small τ then gives no inf − inf)
+            top = lg.masked_fill(~m.bool(), -torch.inf).amax(-1, keepdim=True)
+            raw, lg = lg, (lg - torch.where(m.any(-1, keepdim=True), top, torch.zeros_like(top))) * inv_tau
+        lp = masked_log_softmax(lg, m, dim=-1, stable=stable)
         p = torch.exp(lp) * m
         # rows with no valid entry (target when nothing is attackable): sample index 0, never selected
         p = torch.where(m.any(-1, keepdim=True), p, torch.nn.functional.one_hot(torch.zeros(n, dtype=torch.long,
                                                                                             device=p.device), w).float())
         s = torch.multinomial(p, 1, generator=generator).squeeze(1)
+        if greedy is not None:
+            # first index of the masked maximum (a row with no valid entry: index 0, never selected)
+            cols = torch.arange(w, device=s.device).expand(n, w)
+            first = torch.where(raw.masked_fill(~m.bool(), -torch.inf) == top, cols, w).amin(-1)
+            s = torch.where(greedy, first, s)
         samples[k] = s
         logps[k] = lp.gather(1, s[:, None]).squeeze(1)
     enum = samples['enum']
@@ -74,14 +94,18 @@ def sample_heads(logits: dict, valid: torch.Tensor, U: int, generator=None, stab
     actions[r[move], 3 + N_MOVE_ENUMS + samples['y'][move]] = 1
     actions[r[att], 3 + 2 * N_MOVE_ENUMS + samples['target_unit'][att]] = 1
     logp = logps['enum'] + move * (logps['x'] + logps['y']) + att * logps['target_unit']
+    if greedy is not None:
+        logp = torch.where(greedy, torch.zeros_like(logp), logp)
     masks = (head & valid).to(torch.uint8)
     return samples, actions, masks, logp
 
 
 class PolicyRunner:
-    """Runs a :class:`Policy` for a batch of players on ``device``; keeps no per-player state itself."""
+    """Runs a :class:`Policy` for a batch of players on ``device``; keeps no per-player state itself.
+    ``temperature``: the sampling temperature of steps that give none of their own (1: the policy's softmax, 0:
+    greedy; :func:`sample_heads`)."""
 
-    def __init__(self, policy: Policy, device='cpu', seed: Optional[int] = None):
+    def __init__(self, policy: Policy, device='cpu', seed: Optional[int] = None, temperature: float = 1.0):
         self.policy = policy.to(device).eval()
         self.device = torch.device(device)
         self.generator = torch.Generator(device=self.device)
@@ -89,10 +113,15 @@ class PolicyRunner:
             self.generator.manual_seed(seed)
         self.U = policy.layout.max_units
         self.stable = not policy.config.compat_bugs
+        from .batched import check_temperature
+        self.temperature = float(check_temperature(temperature))
 
     @torch.no_grad()
-    def step(self, env: np.ndarray, units: np.ndarray, handles: np.ndarray, hidden=None):
-        """env (n,3), units (n,U,10), handles (n,U) → (StepOutput, new hidden (h,c) each (n,H) or None)."""
+    def step(self, env: np.ndarray, units: np.ndarray, handles: np.ndarray, hidden=None, temperature=None):
+        """env (n,3), units (n,U,10), handles (n,U) → (StepOutput, new hidden (h,c) each (n,H) or None).
+        ``temperature``: per-row sampling temperature (n,) or a scalar; None: the runner's own."""
+        if temperature is None and self.temperature != 1.0:
+            temperature = self.temperature
         dev = self.device
         e = torch.as_tensor(env, device=dev, dtype=torch.float32)[:, None]
         u = torch.as_tensor(units, device=dev, dtype=torch.float32)[:, None]
@@ -102,7 +131,7 @@ class PolicyRunner:
         logits, value, hn = self.policy.forward_packed(e, u, h)
         valid = batched_action_masks(torch.as_tensor(handles, device=dev))
         samples, actions, masks, logp = sample_heads({k: v[:, 0] for k, v in logits.items()}, valid, self.U,
-                                                     self.generator, self.stable)
+                                                     self.generator, self.stable, temperature)
         out = StepOutput(enum=samples['enum'].cpu().numpy(), x=samples['x'].cpu().numpy(),
                          y=samples['y'].cpu().numpy(), target=samples['target_unit'].cpu().numpy(),
                          actions=actions.cpu().numpy(), masks=masks.cpu().numpy(),

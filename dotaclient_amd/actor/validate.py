@@ -21,14 +21,16 @@ from ..constants import REWARD_KEYS
 
 def evaluate_vs_default_bot(policy, n_games: int = 128, device='cuda', seed: int = 12345,
                             max_dota_time: float = 600.0, threads: int = 8, timeout: float = 600.0,
-                            precision: str = 'fp32') -> Dict[str, float]:
+                            precision: str = 'fp32', temperature: float = 1.0) -> Dict[str, float]:
     """Play ``n_games`` games of ``policy`` (a :class:`~dotaclient_amd.models.policy.Policy`) against the default bot
     and return the reference's validation metrics averaged over the games: ``game/rewards_sum``,
     ``game/rewards_<key>`` for every reward key, ``game/win_rate`` (wins / games), ``game/loss_rate``,
     ``game/steps`` (mean game length) and ``games``. A fixed ``seed`` gives the same games for every policy.
     ``precision``: the policy step the games are played with — by default the IEEE-fp32 actor
     (:class:`~dotaclient_amd.actor.batched.F32ActorPolicy`, the weights as the learner trained them; the reference's
-    validation agent runs the fp32 policy); 5v5 policies fall back to bf16 operands."""
+    validation agent runs the fp32 policy); 5v5 policies fall back to bf16 operands.
+    ``temperature``: the sampling temperature of the evaluated policy (VecActor ``temperature``); 0 is greedy
+    evaluation — the policy's arg-max action every step, so the result does not depend on the sampler's draws."""
     from ..transport.codec import decode
     from .vec import VecActor
     from .weights import WeightStore
@@ -39,7 +41,7 @@ def evaluate_vs_default_bot(policy, n_games: int = 128, device='cuda', seed: int
     mode = 'vs_default_bot_5v5' if policy.config.layout.counts[0] > 1 else 'vs_default_bot'   # 5 heroes a side
     va = VecActor(ws, n_games, msgs.append, device=device, mode=mode, seed=seed,
                   rollout_size=10 ** 9, max_dota_time=max_dota_time, threads=threads, groups=1, stagger=False,
-                  tag=f'val{seed}', precision=precision)
+                  tag=f'val{seed}', precision=precision, temperature=temperature)
     t0 = time.time()
     try:
         while va.games_finished < n_games:
@@ -76,7 +78,8 @@ def evaluate_vs_default_bot(policy, n_games: int = 128, device='cuda', seed: int
 
 def evaluate_vs_snapshot(policy, snapshot_state, n_games: int = 64, device='cuda', seed: int = 777,
                          max_dota_time: float = 600.0, threads: int = 8, timeout: float = 900.0,
-                         precision: str = 'fp32', league_step: str = 'separate') -> Dict[str, float]:
+                         precision: str = 'fp32', league_step: str = 'separate',
+                         temperature: float = 1.0) -> Dict[str, float]:
     """Head-to-head games of ``policy`` (the current weights) against a frozen past snapshot of the same network
     (``snapshot_state``: a state_dict) — the discriminating signal once the default-bot win rate saturates, and one
     entry of the league's win-rate matrix. Every game is a league game of the self-play engine (VecActor with
@@ -84,7 +87,8 @@ def evaluate_vs_snapshot(policy, snapshot_state, n_games: int = 64, device='cuda
     weights; reference mini-league, agent.py:760-765); a fixed ``seed`` replays the same openings. Returns
     ``win_rate`` (wins + ½ time-limit draws, per game), ``wins`` / ``losses`` / ``draws`` and ``games``.
     ``league_step='mixed'``: both versions in ONE policy step per group (VecActor ``league_step``) instead of two —
-    every 1v1 policy, and the 5v5 policy at ``precision='fp32'`` (this function's default)."""
+    every 1v1 policy, and the 5v5 policy at ``precision='fp32'`` (this function's default).
+    ``temperature``: the sampling temperature of both sides (0: both play greedily)."""
     from .league import League
     from .vec import VecActor
     from .weights import WeightStore
@@ -97,7 +101,7 @@ def evaluate_vs_snapshot(policy, snapshot_state, n_games: int = 64, device='cuda
     va = VecActor(ws, n_games, None, device=device, mode=mode, seed=seed, rollout_size=10 ** 9,
                   max_dota_time=max_dota_time, threads=threads, groups=1, stagger=False, league=lg,
                   latest_weights_prob=0.0, opponent_refresh=10 ** 9, tag=f'snap{seed}', precision=precision,
-                  league_step=league_step)
+                  league_step=league_step, temperature=temperature)
     t0 = time.time()
     try:
         while lg.games.get(0, 0.0) < n_games:
@@ -118,11 +122,13 @@ def evaluate_vs_snapshot(policy, snapshot_state, n_games: int = 64, device='cuda
 
 
 def league_matrix(snapshots, config, n_games: int = 32, device='cuda', seed: int = 991, max_dota_time: float = 600.0,
-                  threads: int = 8, precision: str = 'fp32', league_step: str = 'separate') -> Dict[str, object]:
+                  threads: int = 8, precision: str = 'fp32', league_step: str = 'separate',
+                  temperature: float = 1.0) -> Dict[str, object]:
     """Pairwise win rates of league snapshots ``[(label, state_dict), …]`` (oldest first): entry [i][j] is the
     score of snapshot i against snapshot j over ``n_games`` games (wins + ½ draws; [j][i] = 1 − [i][j]). A healthy
     league is (mostly) increasing along each row's diagonal direction: later snapshots beat earlier ones.
-    ``league_step='mixed'`` (1v1, and 5v5 at ``precision='fp32'``): one policy step per group for both snapshots."""
+    ``league_step='mixed'`` (1v1, and 5v5 at ``precision='fp32'``): one policy step per group for both snapshots.
+    ``temperature``: the sampling temperature of both sides of every pair (0: greedy)."""
     from ..models.policy import Policy
     labels = [lab for lab, _ in snapshots]
     n = len(snapshots)
@@ -133,7 +139,7 @@ def league_matrix(snapshots, config, n_games: int = 32, device='cuda', seed: int
         for j in range(i):
             r = evaluate_vs_snapshot(pol, snapshots[j][1], n_games=n_games, device=device, seed=seed + 31 * i + j,
                                      max_dota_time=max_dota_time, threads=threads, precision=precision,
-                                     league_step=league_step)
+                                     league_step=league_step, temperature=temperature)
             m[i][j] = r['win_rate']
             m[j][i] = 1.0 - r['win_rate']
     return {'labels': labels, 'win_rate': m, 'games_per_pair': n_games}

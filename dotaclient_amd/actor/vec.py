@@ -68,6 +68,8 @@ class _Group:
         self.S = self.ve.slots
         self.ppg = self.ve.players_per_game
         self.gp = make_slot_policy(a.policy, self.S, device=a.device, seed=seed, **a._policy_kw())
+        if a.tempered:
+            self.gp.set_temperature(a.temperature)
         self.env = self.gp.h_env.numpy()
         if self.raw:
             # raw unit records staged for the GPU featurizer; the host keeps only the handles (action targets)
@@ -101,6 +103,10 @@ class VecActor:
     features (features/raw.py; the fp8 step their 16-byte form), the step's first kernel featurizes them
     (ops/csrc/featurize.hip), and the rollouts carry the records (``units_raw`` / ``hero``) for the learner's device
     featurization.
+    ``temperature`` / ``opponent_temperature`` (None: the same): the sampling temperature of the slots on the latest
+    weights and of the league opponents' slots — 1 samples the policy's softmax, τ > 0 the softmax of logits / τ (the
+    rollouts carry the log-prob under that behaviour distribution), 0 plays the arg-max action (log-prob 0). With
+    both at 1 (the default) the slot policies are built without the option.
     """
 
     def __init__(self, weight_store, n_games: int, publish: Optional[Callable[[bytes], None]], device='cuda',
@@ -109,7 +115,8 @@ class VecActor:
                  league=None, opponent_refresh: int = 64, start_time: float = -10.0,
                  fog: bool = True, tag: str = 'vec', stagger: bool = False, wire: bool = False,
                  precision: str = 'bf16', ring_sink=None, raw: Optional[bool] = None,
-                 league_step: str = 'separate'):
+                 league_step: str = 'separate', temperature: float = 1.0,
+                 opponent_temperature: Optional[float] = None):
         from .. import native
         if not native.AVAILABLE:
             raise RuntimeError('VecActor needs the native module (python -m dotaclient_amd.native.build)')
@@ -161,6 +168,11 @@ class VecActor:
             raise ValueError("league_step='mixed': the fused entity-attention (5v5) step mixes weight versions at "
                              "precision='fp32' only (the bf16 step's fp32-output encoder has no mixed-set form)")
         self.league_step = league_step
+        from .batched import check_temperature
+        self.temperature = float(check_temperature(temperature))
+        self.opponent_temperature = (self.temperature if opponent_temperature is None
+                                     else float(check_temperature(opponent_temperature)))
+        self.tempered = self.temperature != 1.0 or self.opponent_temperature != 1.0
         groups = max(1, min(int(groups), n_games))
         sizes = [n_games // groups + (1 if i < n_games % groups else 0) for i in range(groups)]
         self.groups = [_Group(self, i, sizes[i], seed * 7919 + i) for i in range(groups)]
@@ -213,6 +225,8 @@ class VecActor:
             kw['raw'] = True
         if self.league_step == 'mixed':
             kw['n_sets'] = 3               # 0: latest weights, 1-2: the two rotating opponent snapshots
+        if self.tempered:
+            kw['temperature'] = True
         return kw
 
     def _sample_opponent(self):
@@ -226,6 +240,8 @@ class VecActor:
         while len(g.opp) <= k:
             gp = make_slot_policy(self.policy, g.S, device=self.device, seed=g.seed + 104729 * (len(g.opp) + 1),
                                   inputs_from=g.gp, **self._policy_kw())
+            if self.tempered:
+                gp.set_temperature(self.opponent_temperature)
             g.opp.append(_Opponent(gp))
         return g.opp[k]
 
@@ -296,6 +312,10 @@ class VecActor:
             opp_slots = np.asarray(g.ve.opponent_slots(), dtype=np.int64)
             if len(opp_slots):
                 hset[opp_slots] = 1 + g.game_opp[opp_slots // g.ppg]
+            if self.temperature != self.opponent_temperature:
+                # slots on the latest weights (set 0) and on the opponent snapshots (sets 1-2)
+                g.gp.set_temperature(np.where(hset == 0, self.temperature, self.opponent_temperature))
+            if len(opp_slots):
                 opp_mask = np.zeros(g.S, bool)
                 opp_mask[opp_slots] = True
                 need = need[~opp_mask[need]]

@@ -3,7 +3,9 @@
 Reference-compatible flags: ``--ip --port --rollout-size --max-dota-time -l/--log --model --use-latest-weights-prob
 --validation --log-dir``. Additional: ``--broker`` (inproc | tcp://host:port | shm://name; default tcp://ip:port),
 ``--env`` (synthetic | grpc://host:port, reference: the dotaservice sidecar on 127.0.0.1:13337), ``--games`` (games
-driven in lockstep with one batched policy step), ``--device``, ``--model-preset``, ``--wire`` (dcx1 | pickle).
+driven in lockstep with one batched policy step), ``--device``, ``--model-preset``, ``--wire`` (dcx1 | pickle),
+``--temperature`` / ``--opponent-temperature`` (sampling temperature of the latest weights / of the opponents on past
+weights; 0 = greedy arg-max play, ``--validation true --temperature 0`` = greedy evaluation).
 
     python -m dotaclient_amd.cli.agent --ip 127.0.0.1 --port 5672 --env synthetic --games 64 --device cuda
 """
@@ -62,6 +64,12 @@ def build_parser():
                     help='vec runtime league opponents: separate = an extra policy step per busy opponent snapshot; '
                          'mixed = one step per group, every slot on its own weight version (1v1 policies; 5v5 with '
                          '--actor-precision fp32)')
+    ap.add_argument('--temperature', type=float, default=1.0,
+                    help='sampling temperature of the policy (vec and service runtimes): 1 samples its softmax, τ > 0 '
+                         'the softmax of logits / τ (within [1e-3, 1e3]), 0 plays the arg-max action; '
+                         '--validation true --temperature 0 is greedy evaluation')
+    ap.add_argument('--opponent-temperature', type=float, default=None,
+                    help='sampling temperature of the opponents that play past weights (default: --temperature)')
     ap.add_argument('--league', type=str, default='oldest', choices=['oldest', 'uniform', 'recent', 'pfsp'],
                     help='opponent sampling over the weight history when not playing the latest weights')
     return ap
@@ -107,13 +115,17 @@ def main(argv=None):
     if device.startswith('cuda') and not torch.cuda.is_available():
         device = 'cpu'
 
+    opp_temperature = args.temperature if args.opponent_temperature is None else args.opponent_temperature
+
     def make_runner(policy):
         seed_r = rng.randrange(1 << 30)
+        # the latest weights play at --temperature, every past version (an opponent) at --opponent-temperature
+        temperature = args.temperature if policy is ws.latest_policy else opp_temperature
         if device.startswith('cuda') and gpu_runner_supported(policy):
             # graph-captured batched GPU step; players' LSTM state lives in device slots
             return GpuRunner(policy.to(device), device=device, seed=seed_r, capacity=max(8, 2 * args.games),
-                             )
-        return PolicyRunner(policy, device=device, seed=seed_r)
+                             temperature=temperature)
+        return PolicyRunner(policy, device=device, seed=seed_r, temperature=temperature)
     runner_for = RunnerCache(make_runner, latest_policy=ws.latest_policy)
     metrics = MetricsWriter(args.log_dir) if (args.validation and args.log_dir) else None
     uploader = None
@@ -163,7 +175,8 @@ def _run_vec(args, ws, broker, league, device, seed, cfg):
                   mode='5v5' if cfg.layout.counts[0] > 1 else '1v1', seed=seed, rollout_size=args.rollout_size,
                   max_dota_time=args.max_dota_time, latest_weights_prob=args.use_latest_weights_prob,
                   hidden_stride=args.hidden_stride, threads=args.threads, league=league, stagger=True,
-                  precision=args.actor_precision, league_step=args.league_step)
+                  precision=args.actor_precision, league_step=args.league_step, temperature=args.temperature,
+                  opponent_temperature=args.opponent_temperature)
     try:
         va.run(n_games=args.n_games)
     except Exception:

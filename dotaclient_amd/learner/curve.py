@@ -39,7 +39,8 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
                        advantages: str = 'vtrace-step', weight_lag: int = 0,
                        replay_recent: int = 0, replay_sampler: str = 'uniform', replay_recent_frac: float = 0.5,
                        replay_priority_alpha: float = 0.6, replay_priority_eta: float = 0.9,
-                       replay_ratio: float = 1.0, league_step: str = 'separate') -> List[Dict]:
+                       replay_ratio: float = 1.0, league_step: str = 'separate',
+                       eval_temperature: float = 1.0) -> List[Dict]:
     """Train for ``budget`` seconds (evaluations excluded) and return the evaluation rows (the first one before
     any training). ``on_row`` is called with every row as it is produced; ``save_model``: path that receives the
     final weights (a reference-format state_dict file). ``eval_precision``: the validation games' policy step.
@@ -57,7 +58,9 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
     ``replay_priority_eta``, ops/replay.py), ``replay_ratio`` > 1 runs that many times more replay steps per
     iteration. ``league_step='mixed'``: league opponents (the actors' and the snapshot evaluations') are stepped in
     the same launch as the latest weights (VecActor ``league_step``; a 5v5 policy: fp32 actor / evaluation precision
-    only)."""
+    only). ``eval_temperature``: the sampling temperature of every evaluation game (default-bot, snapshot and league
+    matrix games; 0: greedy evaluation, both sides of a head-to-head) — the metric names are unchanged and every row
+    carries ``game/eval_temperature``; the training actors are not affected."""
     import json
     import os
 
@@ -140,7 +143,9 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
         sync()
         t0 = time.time()
         row.update(evaluate_vs_default_bot(opt.policy, n_games=eval_games, device=device, seed=eval_seed,
-                                           max_dota_time=max_dota_time, threads=threads, precision=eval_precision))
+                                           max_dota_time=max_dota_time, threads=threads, precision=eval_precision,
+                                           temperature=eval_temperature))
+        row['game/eval_temperature'] = float(eval_temperature)
         t_now = float(row.get('t_train', 0.0))
         for lag in snapshot_lags or ():
             past = [sn for sn in snaps if sn[0] <= t_now - lag + 1e-6]
@@ -148,7 +153,8 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
                 continue
             r = evaluate_vs_snapshot(opt.policy, past[-1][1], n_games=snapshot_games, device=device,
                                      seed=eval_seed + int(lag), max_dota_time=max_dota_time, threads=threads,
-                                     precision=eval_precision, league_step=league_step)
+                                     precision=eval_precision, league_step=league_step,
+                                     temperature=eval_temperature)
             tag = f'{int(lag) // 60}min' if lag >= 60 else f'{int(lag)}s'
             row[f'snap/win_rate_vs_{tag}'] = r['win_rate']
             row[f'snap/age_s_vs_{tag}'] = round(t_now - past[-1][0], 1)
@@ -213,7 +219,8 @@ def run_learning_curve(budget: float = 150.0, eval_every: float = 25.0, eval_gam
             pick = [snaps[round(i * (len(snaps) - 1) / (k - 1))] for i in range(k)]
             lm = league_matrix([(f't{int(t)}s', sd) for t, sd in pick], opt.policy.config,
                                n_games=snapshot_games, device=device, max_dota_time=max_dota_time, threads=threads,
-                               precision=eval_precision, league_step=league_step)
+                               precision=eval_precision, league_step=league_step,
+                               temperature=eval_temperature)
             row = {'league_matrix': lm, 't_train': round(trained, 1)}
             rows.append(row)
             if on_row is not None:

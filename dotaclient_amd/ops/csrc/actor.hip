@@ -52,16 +52,26 @@ __device__ __forceinline__ void load8(const float* p, float* v) {
   v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 
+__device__ __forceinline__ const float* row_temp(const float* temp) { return temp; }
+
 // HT: unit handles int64 (the reference's layout) or int32 (the fp8 step's compact staging); ET: the unit embeddings
-// bf16 (short) or fp32 (the IEEE-fp32 actor step and the 5v5 attention block's output)
-template <typename HT, typename ET>
+// bf16 (short) or fp32 (the IEEE-fp32 actor step and the 5v5 attention block's output).
+// TEMP: a sampling temperature per row, temp[n] = τ (wave-uniform: one wave per row). τ > 0: every head's masked
+// log-softmax over (logit − max) / τ — scaled after the maximum is subtracted, so a small τ gives no inf − inf; τ = 1
+// is bit for bit the TEMP = false kernel — and logp_out the joint log-prob under that tempered (behaviour)
+// distribution. !(τ > 0): greedy — every head's pick is the arg-max of its masked raw logits (lowest index on ties),
+// no RNG call, logp_out = 0 (the τ → 0 limit of the behaviour log-prob). The masks do not depend on τ.
+// The trailing pack is the temperature argument: (const float* temp) with TEMP, nothing without — the TEMP = false
+// kernels keep their argument list and their code.
+template <bool TEMP, typename HT, typename ET, typename... TP>
 __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ z, int ldz,
                                                      const ET* __restrict__ emb,
                                                      const HT* __restrict__ handles, int N, int U,
                                                      unsigned long long seed, const long long* __restrict__ ctr,
                                                      int* __restrict__ idx_out, unsigned char* __restrict__ act_out,
                                                      unsigned char* __restrict__ msk_out, float* __restrict__ logp_out,
-                                                     float* __restrict__ value_out) {
+                                                     float* __restrict__ value_out, TP... temp) {
+  static_assert(sizeof...(TP) == (TEMP ? 1 : 0), "sample_kernel: (const float* temp) with TEMP, no argument without");
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
   const int n = blockIdx.x * 4 + wv;
   if (n >= N) return;
@@ -94,6 +104,13 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ z
   const bool tvalid = lane < U && lane != 0 && handles[(size_t)n * U + lane] != -1;
   const bool any_target = __any(tvalid);
   const unsigned long long c = *ctr;
+  bool greedy = false;
+  float inv_tau = 1.f;
+  if constexpr (TEMP) {
+    const float tau = row_temp(temp...)[n];
+    greedy = !(tau > 0.f);
+    inv_tau = 1.0f / (greedy ? 1.f : tau);
+  }
   const int hoff[4] = {0, 3, 12, 21};
   const int hw[4] = {3, 9, 9, U};
   int pick[4];
@@ -109,10 +126,14 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ z
     float mx = dca::wave_max(v);
     const bool any = mx > -INFINITY;
     if (!any) mx = 0.f;
-    float s = dca::wave_sum(m ? __expf(lg - mx) : 0.f);
+    float d = lg - mx;
+    if constexpr (TEMP) d *= inv_tau;
+    float s = dca::wave_sum(m ? __expf(d) : 0.f);
     if (!(s > 0.f)) s = 1.f;
-    const float lp = lg - mx - __logf(s);
-    const float key = m ? lp + gumbel(seed, c, n, h, lane) : -INFINITY;
+    const float lp = d - __logf(s);
+    float key;
+    if (TEMP && greedy) key = v;
+    else key = m ? lp + gumbel(seed, c, n, h, lane) : -INFINITY;
     int k = wave_argmax(key, lane);
     if (!any) k = 0;
     pick[h] = k;
@@ -136,7 +157,8 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ z
         idx_out[n * 4 + 1] = pick[1];
         idx_out[n * 4 + 2] = pick[2];
         idx_out[n * 4 + 3] = pick[3];
-        logp_out[n] = plogp[0] + (mv ? plogp[1] + plogp[2] : 0.f) + (at ? plogp[3] : 0.f);
+        const float lpj = plogp[0] + (mv ? plogp[1] + plogp[2] : 0.f) + (at ? plogp[3] : 0.f);
+        logp_out[n] = (TEMP && greedy) ? 0.0f : lpj;
         value_out[n] = zr[kQ + 21];
       }
     }
@@ -205,12 +227,21 @@ extern "C" hipError_t dca_actor_state_prep(const short* pre, float* h, float* c,
 extern "C" hipError_t dca_sample_actions(const float* z, int ldz, const void* emb, int emb_f32, const void* handles,
                                          int h32, int N, int U, unsigned long long seed, const long long* ctr,
                                          int* idx, unsigned char* act, unsigned char* msk, float* logp, float* value,
-                                         hipStream_t st) {
+                                         hipStream_t st, const float* temp) {
   if (U < 1 || U > 64 || ldz < kQ + 22) return hipErrorInvalidValue;
   const dim3 grid((N + 3) / 4), block(256);
+  // temp (N) fp32 or nullptr: nullptr launches the TEMP = false kernels
 #define DCA_SAMPLE(HT, ET)                                                                                   \
-  hipLaunchKernelGGL((sample_kernel<HT, ET>), grid, block, 0, st, z, ldz, static_cast<const ET*>(emb),    \
-                     static_cast<const HT*>(handles), N, U, seed, ctr, idx, act, msk, logp, value)
+  do {                                                                                                       \
+    const ET* e = static_cast<const ET*>(emb);                                                               \
+    const HT* hd = static_cast<const HT*>(handles);                                                          \
+    if (temp)                                                                                                \
+      sample_kernel<true, HT, ET><<<grid, block, 0, st>>>(z, ldz, e, hd, N, U, seed, ctr, idx, act, msk,     \
+                                                          logp, value, temp);                                \
+    else                                                                                                     \
+      sample_kernel<false, HT, ET><<<grid, block, 0, st>>>(z, ldz, e, hd, N, U, seed, ctr, idx, act, msk,    \
+                                                           logp, value);                                     \
+  } while (0)
   if (h32) {
     if (emb_f32) DCA_SAMPLE(int, float); else DCA_SAMPLE(int, short);
   } else {

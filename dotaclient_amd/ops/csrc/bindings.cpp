@@ -487,9 +487,11 @@ std::vector<torch::Tensor> encoder_bwd(torch::Tensor units, torch::Tensor w1, to
 // ------------------------------------------------------------------------------------------------------------
 // Actor inference. Fused masked hierarchical sampling: z (N,ldz) f32 head logits [q|enum|x|y|v|pad], emb (N,U,128)
 // bf16, handles (N,U) int64, ctr (1) int64 device step counter; writes idx (N,4) i32, act/msk (N,21+U) u8,
-// logp (N) f32, value (N) f32 (all preallocated so the op is hipGraph-capturable).
+// logp (N) f32, value (N) f32 (all preallocated so the op is hipGraph-capturable). temp: optional (N) f32 sampling
+// temperature per row (τ > 0: tempered softmax, logp under it; otherwise greedy arg-max with logp 0); none: τ = 1.
 void sample_actions(torch::Tensor z, torch::Tensor emb, torch::Tensor handles, int64_t seed, torch::Tensor ctr,
-                    torch::Tensor idx, torch::Tensor act, torch::Tensor msk, torch::Tensor logp, torch::Tensor value) {
+                    torch::Tensor idx, torch::Tensor act, torch::Tensor msk, torch::Tensor logp, torch::Tensor value,
+                    c10::optional<torch::Tensor> temp) {
   CHECK_F32(z); CHECK_DEV(emb); CHECK_CONTIG(emb); CHECK_DEV(handles); CHECK_CONTIG(handles);
   const bool e32 = emb.scalar_type() == at::kFloat;
   TORCH_CHECK(e32 || emb.scalar_type() == at::kBFloat16, "sample_actions: emb bf16 or fp32");
@@ -503,10 +505,16 @@ void sample_actions(torch::Tensor z, torch::Tensor emb, torch::Tensor handles, i
   TORCH_CHECK(idx.size(0) == N && idx.size(1) == 4 && logp.numel() == N && value.numel() == N, "output shapes");
   TORCH_CHECK(act.size(0) == N && act.size(1) == 21 + U && msk.sizes() == act.sizes(), "act/msk (N,21+U)");
   TORCH_CHECK(U <= 64 && ldz >= 150, "U <= 64, ldz >= 150");
+  const float* tp = nullptr;
+  if (temp && temp->defined()) {
+    CHECK_F32(*temp);
+    TORCH_CHECK(temp->numel() == N, "sample_actions: temp must hold one temperature per row (N)");
+    tp = ptr<float>(*temp);
+  }
   hip_check(dca_sample_actions(ptr<float>(z), ldz, emb.data_ptr(), e32 ? 1 : 0, handles.data_ptr(), h32 ? 1 : 0, N,
                                U, (unsigned long long)seed, ptr<long long>(ctr), ptr<int>(idx),
                                ptr<unsigned char>(act), ptr<unsigned char>(msk), ptr<float>(logp), ptr<float>(value),
-                               cur_stream()),
+                               cur_stream(), tp),
             "dca_sample_actions");
 }
 
@@ -1337,7 +1345,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         },
         "exchange-buffer bytes of a team-recurrence launch (0: no such plan)", py::arg("B"), py::arg("H"),
         py::arg("backward"), py::arg("f32"), py::arg("exact") = false, py::arg("rows") = 0);
-  m.def("sample_actions", &sample_actions, "fused masked hierarchical Gumbel-max action sampling (actor)");
+  m.def("sample_actions", &sample_actions, "fused masked hierarchical Gumbel-max action sampling (actor)",
+        py::arg("z"), py::arg("emb"), py::arg("handles"), py::arg("seed"), py::arg("ctr"), py::arg("idx"),
+        py::arg("act"), py::arg("msk"), py::arg("logp"), py::arg("value"), py::arg("temp") = py::none());
   m.def("actor_state_prep", &actor_state_prep, "actor step: state resets + [x | bf16(h)] gate-GEMM operand",
         py::arg("pre"), py::arg("h"), py::arg("c"), py::arg("keep"), py::arg("xh"), py::arg("bump") = py::none());
   m.def("lstm_cell", &lstm_cell, "LSTM cell nonlinearity from fp32 gates (actor single step)", py::arg("gates"),

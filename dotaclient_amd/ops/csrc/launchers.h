@@ -92,7 +92,8 @@ hipError_t dca_lstm_team_bwd(const float* dhs, const float* gates4, const float*
 
 hipError_t dca_sample_actions(const float* z, int ldz, const void* emb, int emb_f32, const void* handles, int h32,
                               int N, int U, unsigned long long seed, const long long* ctr, int* idx,
-                              unsigned char* act, unsigned char* msk, float* logp, float* value, hipStream_t st);
+                              unsigned char* act, unsigned char* msk, float* logp, float* value, hipStream_t st,
+                              const float* temp);   // temp: (N) per-row sampling temperature, or nullptr
 hipError_t dca_actor_core(const void* x896, int x_f32, const void* wpre, const float* bpre, const void* wg,
                           const float* bg, const void* wh, const float* bh, float* h, float* c, const float* keep,
                           const float* active, float* z, int n, int hidden, int linear, int mode, long long* bump,

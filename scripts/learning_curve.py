@@ -53,6 +53,9 @@ def main(argv=None):
                     help='seconds of training: every row also plays the weights from that long ago (comma list, '
                          'empty = off)')
     ap.add_argument('--snapshot-games', type=int, default=64)
+    ap.add_argument('--eval-temperature', type=float, default=1.0,
+                    help='sampling temperature of the evaluation games (default-bot, snapshot, league matrix); 0 = '
+                         'greedy evaluation (arg-max actions, both sides of a head-to-head)')
     ap.add_argument('--old-logp', default='actor', choices=['learner', 'actor'])
     ap.add_argument('--advantages', default='vtrace-step', choices=['vtrace-step', 'vtrace-iteration', 'gae'])
     ap.add_argument('--weight-lag', type=int, default=0,
@@ -85,7 +88,7 @@ def main(argv=None):
                            replay_sampler=a.replay_sampler, replay_recent_frac=a.replay_recent_frac,
                            replay_priority_alpha=a.replay_priority_alpha,
                            replay_priority_eta=a.replay_priority_eta, replay_ratio=a.replay_ratio,
-                           league_matrix_n=a.league_matrix)
+                           league_matrix_n=a.league_matrix, eval_temperature=a.eval_temperature)
 
 
 if __name__ == '__main__':
